@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the StochGPMP inner loop on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A step is ONE planner iteration = one body of the loop at reference planner.py:289-299 (draw S samples per
 particle, evaluate the composite cost, softmax-reweight, update the particle means) on synthetic data.
@@ -12,13 +12,19 @@ particles sharded, no data-path collective; a [64,4]-double statistics all-reduc
 enqueued by sgpmp_step).  With N > 1 and no WORLD_SIZE in the environment the script starts its own N ranks
 BEFORE anything touches the GPU and relays rank 0's line and the exit code.
 
+A plain run sets up, warms up, times the K steps and prints the line: value / ms_per_step (storing mode: every
+iteration writes its samples -- the mode SURVEY.md 8(d)'s algorithmic bytes are defined on).  --dump-outputs DIR
+writes what the timed call returned in its last step (optimize()'s six tensors) as DIR/<name>.npy, a fixed seeded
+sample of the rows where a tensor is large: the inputs are seeded, so two builds can be compared output for output.
+--full adds everything else the benchmark measures, after the timed steps (the --no-* options trim it):
+roofline (event pass), single_iteration_calls, sweep_alone, store_free, parity, cpu_baseline and, at the headline
+configuration, one row per other single-GPU configuration.
+
 Output (rank 0):
   * stdout: ONE compact JSON line, < 4 KB, strict JSON (`compact_line`, tests/test_cpu_host.py holds it to
-    that): value / ms_per_step (storing mode: every iteration writes its samples -- the mode SURVEY.md 8(d)'s
-    algorithmic bytes are defined on), roofline, cpu_baseline, single_iteration_calls, store_free, parity,
-    rccl, one short row per other single-GPU configuration;
-  * bench_detail.json beside this script: everything else -- per-kernel event timings, the counters' sources,
-    the measured CPU points, per-pass times (stderr only says where it went: nothing JSON-shaped besides the line).
+    that): the contract keys, rccl, and with --full the figures above;
+  * with --full, bench_detail.json beside this script: everything else -- per-kernel event timings, the counters'
+    sources, the measured CPU points, per-pass times (stderr only says where it went: nothing JSON-shaped besides the line).
 
 `roofline.frac` = SURVEY 8(d)'s algorithmic bytes of the dominant launch / the TIMED pass's ms_per_step / 8 TB/s
 (a lower bound: the step also holds the update kernel); `launch_ms` is the launch's own average duration from
@@ -80,8 +86,16 @@ def parse(argv=None):
     ap.add_argument("--cpu-particles", type=int, default=4)
     ap.add_argument("--cpu-iters", type=int, default=2)
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="bound of the cpu_baseline leg")
-    ap.add_argument("--detail", default=os.path.join(ROOT, DETAIL_FILE), help="where the detailed record goes")
-    return ap.parse_args(argv)
+    ap.add_argument("--detail", default=os.path.join(ROOT, DETAIL_FILE), help="where the detailed record goes (--full)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the tensors the timed call returned in its last step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other measurement and check (event pass, single-iteration calls, sweep alone, "
+                         "store-free, parity, CPU baseline, other configurations) and write the detailed record")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # --------------------------------------------------------------------------------------- N > 1 launch
@@ -173,6 +187,7 @@ def compact_line(full):
                             "dtype": r.get("dtype")}, 4))
     opt("other_configs", rows or None)
     opt("detail", full.get("detail_file"))
+    opt("kernel_ms_per_step", _clean(full.get("kernel_ms_per_step"), 4))     # (--full: the event pass; what tools/*.sh read)
     out = _clean(out)
     line = json.dumps(out, allow_nan=False, separators=(",", ":"))
     while len(line) >= LINE_LIMIT and optional:
@@ -194,7 +209,8 @@ def emit(full, json_fd, detail_path):
         full["detail_file"] = None
         print(f"bench.py: could not write {detail_path}: {e}", file=sys.stderr)
     # (nothing JSON-shaped goes to stderr: a driver that scans the combined output for the line must find exactly one)
-    print(f"bench.py: detailed record -> {detail_path if full['detail_file'] else '(not written)'}", file=sys.stderr)
+    if detail_path:
+        print(f"bench.py: detailed record -> {detail_path if full['detail_file'] else '(not written)'}", file=sys.stderr)
     line = compact_line(full)
     os.write(json_fd, (line + "\n").encode())
     return line
@@ -271,16 +287,21 @@ def roofline_of(kernel, kernel_ms, N_elems, w, costs_bytes, fused, config_key, s
     return r, detail
 
 
-def kernel_profile(torch, pl, obs, steps, unread=False):
-    """Per-kernel device time with HIP events on the launch stream (a separate pass: the events sit
-    between the kernels, so this pass is never the one whose wall time is reported).  unread: the steps run store-free
-    (what iterations 1 .. K - 1 of an optimize(opt_iters=K) call do)."""
-    pl._engine.profile_enable(True)
+def single_steps(pl, obs, steps, unread=False):
+    """`steps` iterations one call each.  unread: the steps run store-free (what iterations 1 .. K - 1 of an
+    optimize(opt_iters=K) call do)."""
     for _ in range(steps):
         if unread:
             pl.step(_samples_unread=True, **obs)
         else:
             pl.optimize(opt_iters=1, **obs)
+
+
+def kernel_profile(torch, pl, obs, steps, unread=False):
+    """Per-kernel device time with HIP events on the launch stream (a separate pass: the events sit
+    between the kernels, so this pass is never the one whose wall time is reported)."""
+    pl._engine.profile_enable(True)
+    single_steps(pl, obs, steps, unread)
     torch.cuda.synchronize()
     kms, launches = pl._engine.profile_read()
     pl._engine.profile_enable(False)
@@ -288,10 +309,11 @@ def kernel_profile(torch, pl, obs, steps, unread=False):
     return {k: v / launches for k, v in kms.items()}
 
 
-def time_loop(torch, pl, obs, steps, warmup, barrier=None, one_call=True):
+def time_loop(torch, pl, obs, steps, warmup, barrier=None, one_call=True, outputs=None):
     """W warm-up iterations, then exactly `steps` timed iterations between two barriers.  one_call: the loop of
     the reference itself, `optimize(opt_iters=steps)` (planner.py:289-299); else `steps` calls of optimize(opt_iters=1),
-    each returning its own tensors (the loop the reference's example scripts run)."""
+    each returning its own tensors (the loop the reference's example scripts run).  outputs: a list that receives what
+    the last timed call returned."""
     if one_call:
         if warmup:
             pl.optimize(opt_iters=warmup, **obs)
@@ -301,12 +323,41 @@ def time_loop(torch, pl, obs, steps, warmup, barrier=None, one_call=True):
     (barrier or torch.cuda.synchronize)()
     t0 = time.perf_counter()
     if one_call:
-        pl.optimize(opt_iters=steps, **obs)
+        out = pl.optimize(opt_iters=steps, **obs)
     else:
         for _ in range(steps):
-            pl.optimize(opt_iters=1, **obs)
+            out = pl.optimize(opt_iters=1, **obs)
     (barrier or torch.cuda.synchronize)()
-    return time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0
+    if outputs is not None:
+        outputs.append(out)
+    return elapsed
+
+
+OUTPUT_NAMES = ("state_particles", "control_particles", "state_trajectories", "control_samples", "costs", "approx_grad")
+DUMP_BYTES = 60 << 20            # all dumped arrays together
+DUMP_SEED = 0
+
+
+def dump_outputs(torch, outs, out_dir):
+    """optimize()'s tuple of the last timed step -> out_dir/<name>.npy, float32 / float64 as computed (other dtypes as float32).
+    A tensor larger than its share of DUMP_BYTES keeps a fixed seeded sample of its rows: the leading dims flattened, so a row of
+    a [P, S, T, n] tensor is one sampled trajectory [T, n]; the same shape gives the same rows in every run and build."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // len(OUTPUT_NAMES)
+    for name, t in zip(OUTPUT_NAMES, outs):
+        if t is None:
+            continue
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.float()
+        rows = t.flatten(0, -3) if t.dim() >= 3 else t
+        if rows.dim() >= 1 and rows.numel() * rows.element_size() > share:
+            keep = share // (rows[0].numel() * rows.element_size())
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows.shape[0], size=keep, replace=False))
+            rows = rows.index_select(0, torch.as_tensor(idx, device=rows.device))
+        np.save(os.path.join(out_dir, name + ".npy"), rows.cpu().numpy())
 
 
 def store_free_leg(torch, spec_kwargs, dev, config_key, steps, storing_ms, passes=1):
@@ -684,22 +735,35 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # Pass 1: per-kernel device times (HIP events between the kernels; feeds `roofline.launch_ms`).  It runs first so
-    # that the wall-clock pass below starts on a GPU that is already at its working clock: with a cold
+    # Warm-up before the timed pass, so that it starts on a GPU that is already at its working clock: with a cold
     # device the first ~100 iterations run 10-20 % slow, which a 5-step warm-up does not cover.
     # The context's two chain streams (optimize(opt_iters >= 2)) need the same: in a fresh process their first
     # ~150 iterations run up to 25 % slow (tools/first_calls_probe.py), whatever the call sizes.
     for _ in range(2):
         pl.optimize(opt_iters=100, **obs)                 # (device + chain-stream warm-up)
-    kms = kernel_profile(torch, pl, obs, 100, unread=bool(args.store_free))
+    # Pass 1 (--full): per-kernel device times (HIP events between the kernels; feeds `roofline.launch_ms`).  A plain run
+    # steps the same 100 iterations without the events: the timed steps start from the same state either way.
+    kms = None
+    if args.full:
+        kms = kernel_profile(torch, pl, obs, 100, unread=bool(args.store_free))
+    else:
+        single_steps(pl, obs, 100, unread=bool(args.store_free))
     # Pass 2: W untimed warm-up steps, then EXACTLY K timed steps between barriers (the reported value)
     split0 = pl._engine.pipeline_split_steps()
     t_timed = time.perf_counter()
-    elapsed = time_loop(torch, pl, obs, args.steps, args.warmup, barrier, one_call=not args.single_iteration_calls)
+    timed_out = []
+    elapsed = time_loop(torch, pl, obs, args.steps, args.warmup, barrier, one_call=not args.single_iteration_calls,
+                        outputs=timed_out)
     split_steps = pl._engine.pipeline_split_steps() - split0
-    # Pass 3 (reported beside it): the same K iterations as K optimize(opt_iters=1) calls -- the loop of the reference's
-    # example scripts (--store-free: skipped -- single-iteration calls always store)
-    elapsed_calls = time_loop(torch, pl, obs, args.steps, args.warmup, barrier, one_call=False) if not args.store_free else None
+    # what the timed call returned, before anything else runs on the planner's buffers (rank 0: its own shard)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, timed_out[0], args.dump_outputs)
+    del timed_out
+    # Pass 3 (--full, reported beside it): the same K iterations as K optimize(opt_iters=1) calls -- the loop of the
+    # reference's example scripts (--store-free: skipped -- single-iteration calls always store)
+    elapsed_calls = None
+    if args.full and not args.store_free:
+        elapsed_calls = time_loop(torch, pl, obs, args.steps, args.warmup, barrier, one_call=False)
     rank_rates = None
     if use_dist:
         mine = torch.tensor([elapsed, elapsed_calls or 0.0], device="cpu" if shared_gpu else dev, dtype=torch.float64)
@@ -714,46 +778,7 @@ def main():
     comm_lib, comm_hooks = pl._engine.comm_library()     # what the C ABI bound for its collectives ("" = none yet)
 
     if rank == 0:
-        N_elems = P_local * S * T * d
-        sweep_kernel = pl._engine.last_cost_kernel()          # what the dispatcher really launched
-        fused = sweep_kernel.startswith("fused_")
-        is_headline = args.workload == "panda" and (P_local, S, T, args.dtype, args.field, args.spheres, goals) == \
-            (1024, 128, 64, "f32", "rbf", 5, 1)
-        cfg_key = "cfg3" if is_headline else ("cfg2" if (args.workload, P_local, S, T) == ("planar", 256, 64, 128) else
-                                              "cfg5" if (args.workload, P_local, S, T, goals) == ("panda", 512, 256, 128, 4) else
-                                              "cfg3_f64" if (args.workload, P_local, S, T, args.dtype, goals) == ("panda", 1024, 128, 64, "f64", 1) else "")
-        if args.workload == "panda" and cfg_key == "cfg3" and args.field == "sdf":
-            cfg_key = "cfg3_sdf"
-        if cfg_key and sweep_kernel == "fused_step_f64_mixed_kernel":
-            cfg_key += "_mixed"
-        if cfg_key and not fused and args.workload == "panda":
-            cfg_key += "_unfused"
         ms_step = 1e3 * elapsed / args.steps
-        launches_per_iteration = pl._engine.last_step_launches()
-        roof, roof_detail = roofline_of(sweep_kernel, kms["cost_sweep"], N_elems, w, P_local * S * 8, fused,
-                                        cfg_key + ("_store_free" if args.store_free and cfg_key else ""), step_ms=ms_step)
-        # bytes the iteration really moves: K4 reads only the sample rows whose softmax weight is not exactly zero
-        nnz_rows = int((pl._weights_buf != 0).sum())
-        iter_alg = 3 * N_elems * w + 2 * P_local * T * d * w + 2 * P_local * S * 8
-        iter_moved = ((1 if fused else 2) * N_elems * w + nnz_rows * T * d * w + 4 * P_local * T * d * w
-                      + 3 * P_local * S * 8)
-        # the stand-alone sampler and sweep of the same planner (north_star's 40 % clause is about THAT launch)
-        alone = None
-        if world == 1 and fused and not args.no_sweep_alone and not args.store_free:
-            alone = sweep_alone_leg(torch, pl, obs, N_elems, w, P_local * S * 8, config_key=cfg_key)
-        # the store-free mode of the same workload (the product's default inside one optimize() call), beside the headline
-        sfree = None
-        spec = dict(workload=args.workload, P_local=P_local, S=S, T=T, dtype=dtype, field=args.field, spheres=args.spheres,
-                    goals=goals, shard_of=shard_of)
-        if world == 1 and not args.store_free and not args.no_store_free and fused:
-            sfree = store_free_leg(torch, spec, dev, cfg_key, args.steps, ms_step)
-        # free-running K = 10 parity of the benchmarked workload, measured by this run (rank 0 at N = 1, like cpu_baseline)
-        parity = None
-        if world == 1 and not args.no_parity:
-            parity = parity_leg(torch, args, dev, P_local, S, T, goals)
-        cpu = None
-        if world == 1 and not args.no_cpu_baseline:
-            cpu = cpu_baseline(args, torch, S, T, P_local)
         value = world * args.steps / elapsed
         full = {
             "metric": "planner iterations/sec (and ms/iter) at fixed particles x samples x T",
@@ -770,36 +795,78 @@ def main():
                        "parallelism": f"particle-sharded x{world}, RCCL stats all-reduce in sgpmp_step" if world > 1 else "single GPU",
                        "noise": f"philox4x32-{pl._engine.lib.sgpmp_philox_rounds()} + Box-Muller (in-kernel)",
                        "prior_factor_dtype": "f64"},
-            "roofline": roof, "roofline_detail": roof_detail,
-            "cpu_baseline": cpu,
-            "speedup_vs_cpu_baseline": value / cpu["value"] if cpu else None,
-            "single_iteration_calls": {"iterations_per_s": world * args.steps / elapsed_calls,
-                                       "ms_per_step": 1e3 * elapsed_calls / args.steps} if elapsed_calls else None,
+            "roofline": None, "cpu_baseline": None,
             "mode": "store_free" if args.store_free else "storing",
-            "store_free": sfree,
-            "sweep_alone": alone,
-            "parity": parity,
             "rccl": {"ranks": comm_world, "rank": comm_rank, "version": rccl_version, "library": comm_lib,
                      "test_hooks_build": bool(comm_hooks)},
             "shared_gpu_test_double": shared_gpu or bool(comm_hooks and "rccl" not in comm_lib),
             "per_rank_iterations_per_s": None if rank_rates is None else
             {"min": min(rank_rates), "max": max(rank_rates), "all": rank_rates},
-            "kernel_ms_per_step": kms,
-            "launches_per_iteration": launches_per_iteration,
+            "launches_per_iteration": pl._engine.last_step_launches(),
             "loop": {"call": "optimize(opt_iters=1) x K" if args.single_iteration_calls else "optimize(opt_iters=K)",
                      "steps_run_as_two_particle_half_chains": split_steps},
-            "iteration_roofline": {"algorithmic_bytes": iter_alg, "moved_bytes": iter_moved, "k4_rows_read": nnz_rows,
-                                   "moved_GBs": iter_moved / (ms_step * 1e-3) / 1e9,
-                                   "moved_frac_of_hbm_peak": iter_moved / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
             "last_iteration": {"mean_cost_sum": mean_cost, "mean_min_cost": mean_min_cost},
             "timed_region_started_s": t_timed - t_start,
         }
-        if world == 1 and not args.no_other_configs and is_headline:
-            del pl
-            torch.cuda.empty_cache()
-            full["other_configs"] = other_configs(torch, dev)
+        if args.full:
+            N_elems = P_local * S * T * d
+            sweep_kernel = pl._engine.last_cost_kernel()          # what the dispatcher really launched
+            fused = sweep_kernel.startswith("fused_")
+            is_headline = args.workload == "panda" and (P_local, S, T, args.dtype, args.field, args.spheres, goals) == \
+                (1024, 128, 64, "f32", "rbf", 5, 1)
+            cfg_key = "cfg3" if is_headline else ("cfg2" if (args.workload, P_local, S, T) == ("planar", 256, 64, 128) else
+                                                  "cfg5" if (args.workload, P_local, S, T, goals) == ("panda", 512, 256, 128, 4) else
+                                                  "cfg3_f64" if (args.workload, P_local, S, T, args.dtype, goals) == ("panda", 1024, 128, 64, "f64", 1) else "")
+            if args.workload == "panda" and cfg_key == "cfg3" and args.field == "sdf":
+                cfg_key = "cfg3_sdf"
+            if cfg_key and sweep_kernel == "fused_step_f64_mixed_kernel":
+                cfg_key += "_mixed"
+            if cfg_key and not fused and args.workload == "panda":
+                cfg_key += "_unfused"
+            roof, roof_detail = roofline_of(sweep_kernel, kms["cost_sweep"], N_elems, w, P_local * S * 8, fused,
+                                            cfg_key + ("_store_free" if args.store_free and cfg_key else ""), step_ms=ms_step)
+            # bytes the iteration really moves: K4 reads only the sample rows whose softmax weight is not exactly zero
+            nnz_rows = int((pl._weights_buf != 0).sum())
+            iter_alg = 3 * N_elems * w + 2 * P_local * T * d * w + 2 * P_local * S * 8
+            iter_moved = ((1 if fused else 2) * N_elems * w + nnz_rows * T * d * w + 4 * P_local * T * d * w
+                          + 3 * P_local * S * 8)
+            # the stand-alone sampler and sweep of the same planner (north_star's 40 % clause is about THAT launch)
+            alone = None
+            if world == 1 and fused and not args.no_sweep_alone and not args.store_free:
+                alone = sweep_alone_leg(torch, pl, obs, N_elems, w, P_local * S * 8, config_key=cfg_key)
+            # the store-free mode of the same workload (the product's default inside one optimize() call), beside the headline
+            sfree = None
+            spec = dict(workload=args.workload, P_local=P_local, S=S, T=T, dtype=dtype, field=args.field, spheres=args.spheres,
+                        goals=goals, shard_of=shard_of)
+            if world == 1 and not args.store_free and not args.no_store_free and fused:
+                sfree = store_free_leg(torch, spec, dev, cfg_key, args.steps, ms_step)
+            # free-running K = 10 parity of the benchmarked workload, measured by this run (rank 0 at N = 1, like cpu_baseline)
+            parity = None
+            if world == 1 and not args.no_parity:
+                parity = parity_leg(torch, args, dev, P_local, S, T, goals)
+            cpu = None
+            if world == 1 and not args.no_cpu_baseline:
+                cpu = cpu_baseline(args, torch, S, T, P_local)
+            full.update({
+                "roofline": roof, "roofline_detail": roof_detail,
+                "cpu_baseline": cpu,
+                "speedup_vs_cpu_baseline": value / cpu["value"] if cpu else None,
+                "single_iteration_calls": {"iterations_per_s": world * args.steps / elapsed_calls,
+                                           "ms_per_step": 1e3 * elapsed_calls / args.steps} if elapsed_calls else None,
+                "store_free": sfree,
+                "sweep_alone": alone,
+                "parity": parity,
+                "kernel_ms_per_step": kms,
+                "iteration_roofline": {"algorithmic_bytes": iter_alg, "moved_bytes": iter_moved, "k4_rows_read": nnz_rows,
+                                       "moved_GBs": iter_moved / (ms_step * 1e-3) / 1e9,
+                                       "moved_frac_of_hbm_peak": iter_moved / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
+            })
+            if world == 1 and not args.no_other_configs and is_headline:
+                del pl
+                torch.cuda.empty_cache()
+                full["other_configs"] = other_configs(torch, dev)
         full["wall_seconds"] = time.perf_counter() - t_start
-        emit(full, json_fd, args.detail if world == 1 or not shared_gpu else None)
+        emit(full, json_fd, args.detail if args.full and (world == 1 or not shared_gpu) else None)
     # the context (and its RCCL communicator) goes before torch's process group does
     pl = None
     import gc

@@ -575,12 +575,42 @@ def gen_signatures():
         json.dump(out, f, indent=1, sort_keys=True)
 
 
+# ------------------------------------------------------------------------------ G12
+G12_BRANCHES = {"generic": "COMPATIBLE", "avx2": "AVX2"}       # record name -> MKL_CBWR
+
+
+def gen_panda_fk_mkl_branches():
+    """g4's Panda FK on the other roundings MKL's code branches (MKL_CBWR) give its small GEMMs.  With MKL 2024.2 every branch
+    name gives one of three: AVX-512 (AUTO on an AVX-512 host, AVX512, AVX512_E1 .. E5: g4's fk_oracle, the run the reference
+    was fed), "avx2" (AVX2, AVX512_MIC) and "generic" (COMPATIBLE, SSE2 .. SSE4_2, AVX).  MKL reads the setting once per
+    process, so a child process computes each run.  Data only: the oracle's output on g4's trajectories."""
+    part = os.environ.get("G12_PART")
+    if part:                                     # (the child: one branch, MKL_CBWR set by the parent)
+        z = np.load(os.path.join(OUT, "g4_panda_fields.npz"))
+        n = 7
+        np.savez(part, **{tag: npy(fk_all_links(torch.as_tensor(z[f"panda/{tag}/trajs"], dtype=dtype).reshape(-1, 2 * n)[:, :n]))
+                          for tag, dtype in (("f64", torch.float64), ("f32", torch.float32))})
+        return
+    import subprocess
+    import tempfile
+    out = {}
+    with tempfile.TemporaryDirectory() as d:
+        for name, cbwr in G12_BRANCHES.items():
+            path = os.path.join(d, name + ".npz")
+            subprocess.run([sys.executable, os.path.abspath(__file__), "g12"], env=dict(os.environ, MKL_CBWR=cbwr, G12_PART=path),
+                           check=True, stdout=subprocess.DEVNULL)
+            with np.load(path) as runs:
+                out.update({f"{name}/panda/{tag}/fk_oracle": runs[tag] for tag in runs.files})
+    np.savez_compressed(os.path.join(OUT, "g12_panda_fk_mkl_branches.npz"), **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(1)
     gens = {"g1": gen_prior, "g2": gen_planar_e2e, "g3": gen_cost_terms, "g4": gen_panda_fields,
             "g5": gen_update_and_is, "g6": gen_scene_tooling, "g7": gen_gpmp, "g8": gen_field_surface,
-            "g9": gen_panda_urdf, "g10": gen_per_particle_precisions, "g11": gen_signatures}
+            "g9": gen_panda_urdf, "g10": gen_per_particle_precisions, "g11": gen_signatures,
+            "g12": gen_panda_fk_mkl_branches}
     for key in (sys.argv[1:] or sorted(gens, key=lambda k: int(k[1:]))):          # `python oracle/gen_golden.py g6` regenerates one
         gens[key]()
     for f in sorted(os.listdir(OUT)):

@@ -337,6 +337,7 @@ def test_bench_line_is_compact_strict_json_with_the_contract_keys(tmp_path):
     assert rec["rccl"]["ranks"] == 8 and len(rec["per_rank_iterations_per_s"]["all"]) == 8
     assert rec["per_rank_iterations_per_s"]["min"] == full["per_rank_iterations_per_s"]["min"]          # (not rounded)
     assert rec["sweep_alone_frac"] == pytest.approx(0.4541, rel=1e-3)
+    assert rec["kernel_ms_per_step"] == full["kernel_ms_per_step"]                       # (what tools/*.sh read)
     assert [set(r) for r in rec["other_configs"]] == [{"config", "it_per_s", "store_free_it_per_s", "frac", "bound", "kernel",
                                                        "dtype"}] * 3
     # a record that grew (forty configurations) loses optional parts, never the contract keys, and stays under the limit
@@ -355,6 +356,36 @@ def test_bench_line_is_compact_strict_json_with_the_contract_keys(tmp_path):
     det = json.loads(open(detail).read(), parse_constant=no_constants)
     assert det["roofline_detail"]["algorithmic_bytes_per_launch"] == 940572672 and det["cpu_baseline"]["leg_seconds"] is None
     assert json.loads(out)["detail"] == "bench_detail.json"
+
+
+def test_bench_dump_outputs_is_bounded_and_seeded(tmp_path):
+    """`bench.py --dump-outputs`: optimize()'s six tensors (here CPU tensors of config 3's shapes, views of the same buffers)
+    -> <name>.npy, float32 / float64 as computed; the sample-sized ones keep a seeded sample of their rows -- the same rows
+    whatever the values -- and all files together stay within 64 MB."""
+    import numpy as np
+    import bench
+    P, S, T, n = 1024, 128, 64, 7
+    g = torch.Generator().manual_seed(0)
+    samples, means = torch.randn(P, S, T, 2 * n, generator=g), torch.randn(P, T, 2 * n, generator=g, dtype=torch.float64)
+    outs = (means[..., :n], means[..., -n:], samples[..., :n], samples[..., -n:], torch.randn(P, S, generator=g),
+            torch.randn(P, T, 2 * n, generator=g))
+    bench.dump_outputs(torch, outs, str(tmp_path / "a"))
+    bench.dump_outputs(torch, tuple(2 * t for t in outs), str(tmp_path / "b"))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(f"{k}.npy" for k in bench.OUTPUT_NAMES)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64e6
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    again = {f[:-4]: np.load(tmp_path / "b" / f) for f in files}
+    assert got["state_particles"].dtype == np.float64 and np.array_equal(got["state_particles"], means[..., :n].numpy())
+    assert got["costs"].dtype == np.float32 and np.array_equal(got["costs"], outs[4].numpy())
+    st = got["state_trajectories"]
+    assert st.dtype == np.float32 and 1000 < st.shape[0] < P * S and st.shape[1:] == (T, n)
+    rows = samples[..., :n].reshape(P * S, T, n).numpy()
+    picked = [int(np.flatnonzero((rows[:, 0, 0] == r[0, 0]))[0]) for r in st[:50]]
+    assert np.array_equal(st[:50], rows[picked]) and picked == sorted(picked)            # whole rows, in order
+    assert np.array_equal(2 * st, again["state_trajectories"])                               # the same rows
+    controls = samples[..., -n:].reshape(P * S, T, n).numpy()
+    assert np.array_equal(got["control_samples"][:50], controls[picked])                    # state and control of one sample
 
 
 def test_bench_multi_gpu_launch_starts_ranks_and_relays_failure():

@@ -323,7 +323,7 @@ def test_bench_single_rank_rccl_smoke():
     dispatcher's kernel name (not a Python re-derivation)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(SGPMP_BENCH_FORCE_DIST="1", MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full",
                         "--no-cpu-baseline", "--no-other-configs", "--particles", "128"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-4000:]
@@ -332,3 +332,39 @@ def test_bench_single_rank_rccl_smoke():
     line = json.loads(lines[0])
     assert line["n_gpus"] == 1 and "fused_step_kernel" in line["roofline"]["kernel"]
     assert line["roofline"]["frac"] > 0 and line["last_iteration"]["mean_cost_sum"] > 0
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_what_they_returned(tmp_path):
+    """A plain bench.py run (no --full): one line with the contract keys and none of --full's figures, no detailed record;
+    --dump-outputs writes optimize()'s six tensors of the last timed step as float32 .npy files within the size bound, and a
+    second process with the same arguments writes the same arrays, bit for bit."""
+    import numpy as np
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    detail = tmp_path / "detail.json"
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"outputs{i}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "3", "--particles", "128",
+                            "--dump-outputs", str(out), "--detail", str(detail)],
+                           env=env, capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-4000:]
+        lines = p.stdout.strip().splitlines()
+        assert len(lines) == 1, lines
+        line = json.loads(lines[0])
+        assert line["steps"] == 7 and line["warmup"] == 3 and line["dtype"] == "f32" and line["higher_is_better"] is True
+        assert line["unit"] == "iterations/s" and line["ms_per_step"] > 0
+        assert abs(line["value"] - 1e3 / line["ms_per_step"]) <= 1e-9 * line["value"]
+        assert line["roofline"] is None and line["cpu_baseline"] is None
+        assert not {"parity", "store_free", "sweep_alone", "single_iteration_calls", "other_configs", "kernel_ms_per_step"} & set(line)
+        assert not detail.exists()
+        got = {n: np.load(out / f"{n}.npy") for n in bench.OUTPUT_NAMES}
+        assert sum(a.nbytes for a in got.values()) <= 64e6
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+        assert got["costs"].shape == (128, 128) and got["state_particles"].shape == (128, 64, 7)
+        assert got["approx_grad"].shape == (128, 64, 14)
+        rows = bench.DUMP_BYTES // len(bench.OUTPUT_NAMES) // (64 * 7 * 4)      # (128 x 128 sample rows: a seeded sample)
+        assert got["state_trajectories"].shape == got["control_samples"].shape == (rows, 64, 7)
+        runs.append(got)
+    for n in bench.OUTPUT_NAMES:
+        assert np.array_equal(runs[0][n], runs[1][n]), n

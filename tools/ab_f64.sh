@@ -5,11 +5,11 @@ LIBS=${@:-stoch_gpmp_amd/libsgpmp.so}
 for rep in 1 2 3; do
 for lib in $LIBS; do
   for opt in 0 1; do
-  SGPMP_F64_FIELDS_F32=$opt SGPMP_LIB_PATH=$PWD/$lib python3 bench.py --dtype f64 --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline --no-parity --no-sweep-alone --no-store-free 2>/dev/null | python3 -c "
+  SGPMP_F64_FIELDS_F32=$opt SGPMP_LIB_PATH=$PWD/$lib python3 bench.py --full --dtype f64 --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline --no-parity --no-sweep-alone --no-store-free 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$lib', 'fields-f32' if $opt else 'all-fp64', round(d['value'],1), round(d['ms_per_step'],5), d['roofline']['launch_ms'])"
   done
-  SGPMP_LIB_PATH=$PWD/$lib python3 bench.py --workload planar --dtype f64 --steps 100 --no-other-configs --no-cpu-baseline --no-parity --no-sweep-alone --no-store-free 2>/dev/null | python3 -c "
+  SGPMP_LIB_PATH=$PWD/$lib python3 bench.py --full --workload planar --dtype f64 --steps 100 --no-other-configs --no-cpu-baseline --no-parity --no-sweep-alone --no-store-free 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$lib', 'planar-256x64x128', round(d['value'],1), round(d['ms_per_step'],5), d['roofline']['launch_ms'])"
 done; done

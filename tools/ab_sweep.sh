@@ -4,7 +4,7 @@
 LIBS=${@:-stoch_gpmp_amd/libsgpmp.so}
 for rep in 1 2 3; do
 for lib in $LIBS; do
-  SGPMP_LIB_PATH=$PWD/$lib python3 bench.py --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline --no-parity --no-store-free 2>/dev/null | python3 -c "
+  SGPMP_LIB_PATH=$PWD/$lib python3 bench.py --full --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline --no-parity --no-store-free 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); a=d['sweep_alone']; print('$lib', 'sweep', a['launch_ms'], a['frac'], 'sampler', a['sampler_launch_ms'], 'step it/s', round(d['value'],1))"
 done; done

@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/chain_tl
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace --output-format csv -d "$OUT/tr" -o tr -- python3 $ROOT/bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-other-configs --no-parity ${ARGS:-} > "$OUT/bench.json" 2> "$OUT/log.txt"
+rocprofv3 --kernel-trace --output-format csv -d "$OUT/tr" -o tr -- python3 $ROOT/bench.py --full --steps 60 --warmup 10 --no-cpu-baseline --no-other-configs --no-parity ${ARGS:-} > "$OUT/bench.json" 2> "$OUT/log.txt"
 cd "$ROOT"
 python3 tools/chain_timeline.py "$OUT/tr" > gpurun_out/chain_timeline.txt 2>&1
 rm -rf "$OUT/tr"

@@ -2,7 +2,7 @@
 # Clock and power of the GPU while the planner loop runs (is the fused launch power-bound?): runs a bench configuration in
 # the background and samples rocm-smi.  usage: power_probe.sh "<env>" "<bench args>"
 ENVV="$1"; ARGS="$2"
-( env $ENVV python3 bench.py --steps 6000 --warmup 20 --no-other-configs --no-cpu-baseline --no-parity $ARGS > /tmp/power_probe_bench.json 2>/dev/null ) &
+( env $ENVV python3 bench.py --full --steps 6000 --warmup 20 --no-other-configs --no-cpu-baseline --no-parity $ARGS > /tmp/power_probe_bench.json 2>/dev/null ) &
 BP=$!
 sleep 14
 for i in 1 2 3 4 5 6; do

@@ -3,7 +3,7 @@
 # sum of kernel times with the wall time per iteration.
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/prof_c1; mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o c1 -- python3 $ROOT/bench.py --workload planar --particles 4 --samples 16 --traj-len 64 --dtype f64 --steps 500 --warmup 50 --no-cpu-baseline > $OUT/bench.json 2> $OUT/log.txt
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o c1 -- python3 $ROOT/bench.py --full --workload planar --particles 4 --samples 16 --traj-len 64 --dtype f64 --steps 500 --warmup 50 --no-cpu-baseline > $OUT/bench.json 2> $OUT/log.txt
 cd $ROOT
 python3 - <<'PY'
 import csv, glob, json

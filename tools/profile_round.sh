@@ -10,7 +10,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-other-configs --no-parity"
+BENCH="python3 $ROOT/bench.py --full --steps 60 --warmup 10 --no-cpu-baseline --no-other-configs --no-parity"
 
 # Per-kernel figures want whole-range launches: inside optimize(opt_iters=K) the context runs two half-range launch
 # sequences that overlap each other (csrc/api.hip StepPipe), which stretches each launch's duration in a trace.
@@ -29,7 +29,7 @@ for grp in "FETCH_SIZE" "WRITE_SIZE" \
 done
 cd "$ROOT"
 unset SGPMP_NO_STEP_PIPELINE
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > "$OUT/bench_driver_like_steps20_warmup5.json" 2> /dev/null
-python3 bench.py --steps 200 --warmup 20 > "$OUT/bench_with_cpu_baseline.json" 2> "$OUT/bench.log"
+python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > "$OUT/bench_driver_like_steps20_warmup5.json" 2> /dev/null
+python3 bench.py --full --steps 200 --warmup 20 > "$OUT/bench_with_cpu_baseline.json" 2> "$OUT/bench.log"
 python3 tools/summarise_prof.py "$OUT" > "$OUT/summary.txt" 2>&1
 tail -40 "$OUT/summary.txt"
