@@ -24,7 +24,7 @@ from stoch_gpmp_amd.costs.fields import (EESE3DistanceField, LinkDistanceField, 
                                          LinkSelfDistanceField)
 from stoch_gpmp_amd.envs.spheres import random_init_static_sphere  # noqa: E402
 from stoch_gpmp_amd.planner import StochGPMP, print_info  # noqa: E402
-from stoch_gpmp_amd.robots.panda import DifferentiableFrankaPanda  # noqa: E402
+from stoch_gpmp_amd.robots.panda import PANDA_Q_LIMITS, PANDA_V_LIMITS, DifferentiableFrankaPanda  # noqa: E402
 
 
 def main(opt_iters=500, seed=None, num_particles_per_goal=5, num_samples=32, num_obst=5, traj_len=64,
@@ -85,6 +85,15 @@ def main(opt_iters=500, seed=None, num_particles_per_goal=5, num_samples=32, num
         ee = panda_fk.compute_forward_kinematics_all_links(planner.particle_means[:, -1, :n_dof].contiguous())[:, -1, :3, 3]
         print("end-effector distance to target per particle [m]:",
               [round(float(v), 4) for v in (ee - target_H[:3, 3]).norm(dim=-1)])
+        # which particle could the robot execute?  every state of the GP-interpolated trajectories (4 inserted per interval)
+        # against the spheres, the arm itself and the joint / velocity limits (no reference counterpart)
+        best = planner.best_trajectories(n_sub=4, q_limits=PANDA_Q_LIMITS, v_limits=PANDA_V_LIMITS, **obs)
+        for g, p in enumerate(best.index.tolist()):
+            if p < 0:
+                print(f"goal {g}: no valid particle")
+            else:
+                print(f"goal {g}: best valid particle {p}, cost {float(best.cost[g]):.4f}, "
+                      f"clearance {float(best.validity.clearance[p]):.4f} m")
     return planner, costs
 
 

@@ -448,6 +448,35 @@ int sgpmp_link_distances(sgpmp_ctx* ctx, const void* frames, int64_t batch, int 
 int sgpmp_field_grad(sgpmp_ctx* ctx, int term, const void* q, int64_t batch, const void* spheres,
                      int n_spheres, void* value, void* grad, void* stream);
 
+/* ---- dense trajectories: GP interpolation between the support waypoints, and a check of ALL fine states ---- */
+/* No reference counterpart: the reference evaluates every collision term at the T support waypoints only (cost_functions.py:
+ * 247-261) and has no joint or velocity limits.  The interpolant is the one the planner's own prior implies: the posterior mean
+ * of the constant-velocity GP between two support states, x(tau) = Lambda(tau) x_i + Psi(tau) x_{i+1} (the GPMP "GP
+ * interpolation"); for this prior Q_c and the prior mean cancel and the result is the cubic Hermite spline on (q, q'), so only
+ * `dt` is needed.  n_sub = k >= 0 points are inserted per interval: T_f = (T - 1)(k + 1) + 1 fine states, fine index
+ * f = i (k + 1) + m at s = m / (k + 1) of interval i; support states (m = 0, and f = T_f - 1) are copied, not computed.  Both
+ * entry points evaluate the fine states with the same device function (csrc/traj_dense.hip: hermite_state), bit for bit. */
+#define SGPMP_MAX_SUBSTEPS 31
+/* trajs [B,T,d] -> out [B,T_f,d], ctx dtype, T = dims.traj_len. */
+int sgpmp_interpolate(sgpmp_ctx* ctx, const void* trajs, int64_t batch, int n_sub, double dt, void* out, void* stream);
+/* Per trajectory, over ALL T_f fine states (never written to memory): values [B,4] ctx dtype, where [B,4] int32 = the first fine
+ * index attaining each value (ties go to the lowest f).
+ *   [0] c_obs   min over f, links l, spheres o of |p_l(q_f) - c_o| - r_o   (the D of sgpmp_link_distances; needs sgpmp_set_fk and spheres)
+ *   [1] c_self  min over f and link pairs i - j >= 2 whose distance depends on q of |p_i - p_j|   (needs sgpmp_set_fk; rigid and
+ *               coincident pairs are left out: with them the minimum is a constant of the chain)
+ *   [2] e_lim   max over f, dof k of max(q_lo[k] - q, q - q_hi[k], |q'| - v_max[k]), over whichever limits are given
+ *   [3] g_occ   max over f of the grid value of cost term `grid_term` at (q_f0, q_f1)   (sgpmp_grid_lookup's value)
+ * A column whose inputs are absent reports +inf ([0], [1]) or -inf ([2], [3]) with where = -1.  A trajectory with any non-finite
+ * fine state reports NaN in all four columns and the first non-finite fine index in all four `where`.
+ * SGPMP_EINVAL: n_sub outside [0, SGPMP_MAX_SUBSTEPS], dt <= 0, a null buffer with batch > 0, grid_term >= 0 that is not a GRID
+ * term; SGPMP_ESTATE: spheres without a chain. */
+int sgpmp_validate(sgpmp_ctx* ctx, const void* trajs, int64_t batch, int n_sub, double dt,
+                   const void* spheres, int n_spheres,      /* DEVICE [n,4] or NULL          */
+                   int grid_term,                           /* index of a GRID cost term, -1 */
+                   const double* q_lo, const double* q_hi,  /* HOST [n_dof] or NULL          */
+                   const double* v_max,                     /* HOST [n_dof] or NULL          */
+                   void* values, int32_t* where, void* stream);
+
 /* ---- GPMP: the reference's Gauss-Newton planner (planner.py:352-661) ------- */
 /* First half of GPMP._step (planner.py:580-581, cost.get_linear_system): evaluates every smooth link
  * field of the cost list and its Jacobian at waypoints 1..T-1 of the particle means [P,T,d] (kept in

@@ -17,6 +17,7 @@ FIELD_RBF, FIELD_SDF, FIELD_OCCUPANCY = 0, 1, 2
 FLAG_GP_START, FLAG_SDF_CLAMP, FLAG_EE_SQUARE = 1, 16, 32
 MAX_TERMS, MAX_JOINTS, MAX_DOF, MAX_INTERP = 8, 16, 8, 8
 STAT_SHARDS = 64
+MAX_SUBSTEPS = 31                    # include/sgpmp.h SGPMP_MAX_SUBSTEPS
 OK, EINVAL, ENOTPD, EHIP, ESTATE = 0, -1, -2, -3, -4
 STEP_MEANS_KEPT = 1
 STEP_NO_SAMPLES = 2
@@ -101,6 +102,8 @@ SIGNATURES = {
     "sgpmp_field_eval": (_I, [_P, _I, _P, _I64, _I, _P, _I, _P, _P]),
     "sgpmp_link_distances": (_I, [_P, _P, _I64, _I, _P, _I, _I, _D, _P, _P]),
     "sgpmp_field_grad": (_I, [_P, _I, _P, _I64, _P, _I, _P, _P, _P]),
+    "sgpmp_interpolate": (_I, [_P, _P, _I64, _I, _D, _P, _P]),
+    "sgpmp_validate": (_I, [_P, _P, _I64, _I, _D, _P, _I, _I, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), _P, _P, _P]),
     "sgpmp_gpmp_linearize": (_I, [_P, _P, _P, _I, _P, _P]),
     "sgpmp_gpmp_solve": (_I, [_P, _P, _P, C.c_double, C.c_double, _P, _P, _P]),
     "sgpmp_event_create": (_I, [C.POINTER(_P)]),

@@ -102,6 +102,8 @@ struct sgpmp_ctx {
     int last_step_launches = 0;      // kernels the last sgpmp_step enqueued for its particle range (1: everything in one launch)
     hipStream_t k1_side = nullptr;   // sgpmp_set_priors: the second factorisation's stream
     hipEvent_t k1_fork = nullptr;
+    // link pairs (i, j), i - j >= 2, whose distance depends on q: bit j of word i (sgpmp_validate's self-clearance column)
+    uint32_t pair_mask[SGPMP_MAX_LINKS] = {};
 };
 
 // name -> field of SgpmpToggles (environment variable = "SGPMP_" + upper-case name)
@@ -789,6 +791,38 @@ static void analyse_chain(ChainDev& ch) {
     }
 }
 
+// The link pairs a self-CLEARANCE has to look at (traj_dense.hip): i - j >= 2 (torch.tril(.., diagonal=-2), fields.py:106) and a
+// distance that moves with q, by the probe of analyse_chain -- but over ALL links, not the representatives of coincident
+// clusters: (8, 6) on the Panda is such a pair although link 8 always sits on link 7, whose pair (7, 6) is adjacent.
+static void moving_pair_mask(const ChainDev& ch, uint32_t* mask) {
+    const int L = ch.n_links, K = 24;
+    int nrev = 0;
+    for (int j = 0; j < ch.n_joints; ++j) nrev += ch.j[j].revolute ? 1 : 0;
+    std::vector<double> d2min((size_t)L * L, 1e300), d2max((size_t)L * L, 0.);
+    uint64_t lcg = 0x9E3779B97F4A7C15ull;
+    for (int k = 0; k < K; ++k) {
+        double q[SGPMP_MAX_JOINTS], pos[SGPMP_MAX_LINKS][3];
+        for (int i = 0; i < nrev; ++i) {
+            lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+            q[i] = ((double)(lcg >> 11) / 9007199254740992.0 * 2. - 1.) * 3.0;
+        }
+        host_fk_points(ch, q, pos);
+        for (int i = 0; i < L; ++i)
+            for (int j = 0; j < i; ++j) {
+                double d2 = 0.;
+                for (int a = 0; a < 3; ++a) d2 += (pos[i][a] - pos[j][a]) * (pos[i][a] - pos[j][a]);
+                const size_t e = (size_t)i * L + j;
+                d2min[e] = std::min(d2min[e], d2); d2max[e] = std::max(d2max[e], d2);
+            }
+    }
+    for (int i = 0; i < SGPMP_MAX_LINKS; ++i) mask[i] = 0;
+    for (int i = 2; i < L; ++i)
+        for (int j = 0; j + 2 <= i; ++j) {
+            const size_t e = (size_t)i * L + j;
+            if (d2max[e] - d2min[e] > 1e-12 * std::max(1., d2max[e])) mask[i] |= 1u << j;
+        }
+}
+
 extern "C" int sgpmp_set_fk(sgpmp_ctx* c, const sgpmp_joint* chain, int n_joints) {
     if (!c || !chain) return fail(SGPMP_EINVAL, "sgpmp_set_fk: null argument");
     if (n_joints < 1 || n_joints > SGPMP_MAX_JOINTS)
@@ -822,6 +856,7 @@ extern "C" int sgpmp_set_fk(sgpmp_ctx* c, const sgpmp_joint* chain, int n_joints
         if (same) ch.plan.codegen_id = 1;
     }
     c->h_chain = ch;
+    moving_pair_mask(ch, c->pair_mask);
     HIPCHK(hipMemcpy(c->d_chain, &ch, sizeof(ch), hipMemcpyHostToDevice));
     c->have_chain = true;
     c->prog_dirty = true;
@@ -905,6 +940,21 @@ static int finalize_program(sgpmp_ctx* c) {
     c->prog_dirty = false;
     return SGPMP_OK;
 }
+
+// What the entry points outside this file (traj_dense.hip) may see of a context, and how they report errors.
+int sgpmp_ctx_view(sgpmp_ctx* c, SgpmpCtxView* out) {
+    std::memset(out, 0, sizeof(*out));
+    out->dims = c->dims;
+    out->have_chain = c->have_chain ? 1 : 0;
+    out->h_chain = &c->h_chain;
+    out->d_chain = c->d_chain;
+    out->pair_mask = c->pair_mask;
+    if (!c->have_costs) return SGPMP_OK;
+    const int rc = finalize_program(c);
+    if (rc == SGPMP_OK) out->prog = &c->h_prog;
+    return rc;
+}
+int sgpmp_set_error(int code, const char* msg) { return fail(code, msg); }
 
 extern "C" int sgpmp_sample(sgpmp_ctx* c, int which, uint64_t seed, uint64_t draw, const void* means,
                             int n_modes, int mode_offset, int n_samples, const void* eps, int eps_modes,

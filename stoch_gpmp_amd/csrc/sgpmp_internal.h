@@ -157,6 +157,21 @@ const char* comm_step_end(SgpmpComm* c, double* stats, bool two_halves);
 const char* comm_stats_wait(SgpmpComm* c, double* stats, hipStream_t stream);
 const char* comm_allgather(SgpmpComm* c, const void* send, void* recv, size_t bytes, hipStream_t stream);
 
+// ---------------------------------------------------------------------------------- context view (api.hip)
+// `struct sgpmp_ctx` is private to api.hip; entry points that live next to their kernels (traj_dense.hip) read a context through
+// this view and report through sgpmp_set_error (the message sgpmp_last_error() returns; the code is handed back).
+struct SgpmpCtxView {
+    sgpmp_dims dims;
+    int have_chain;
+    const ChainDev* h_chain;      // HOST copy of the chain (valid when have_chain)
+    const ChainDev* d_chain;      // DEVICE copy
+    const CostProgram* prog;      // HOST, finalized (point counts resolved, pushed to the device); null: no cost program set
+    const uint32_t* pair_mask;    // [SGPMP_MAX_LINKS] bit j of word i: links i - j >= 2 whose distance depends on q
+};
+// fills *out; runs finalize_program when costs are set and returns its status (out->prog stays null when it fails)
+int sgpmp_ctx_view(sgpmp_ctx* c, SgpmpCtxView* out);
+int sgpmp_set_error(int code, const char* msg);
+
 // ---------------------------------------------------------------------------------- run-time chain kernels (chain_rtc.hip)
 struct RtcChain;
 const char* rtc_chain_get(const char* struct_src, int n_dof, RtcChain** out);       // null on success, else the reason

@@ -1,0 +1,61 @@
+"""Host-side arithmetic of the dense (GP-interpolated) trajectories: index bookkeeping and the interpolation weights that
+`sgpmp_interpolate` / `sgpmp_validate` (csrc/traj_dense.hip) apply on the GPU.  numpy only, no GPU, no library.
+
+Between two support states x_i = (q_i, v_i) and x_{i+1}, `dt` apart, the posterior mean of the constant-velocity GP prior is
+
+    x(tau) = Lambda(tau) x_i + Psi(tau) x_{i+1},  Psi = Q(tau) Phi(dt - tau)^T Q(dt)^-1,  Lambda = Phi(tau) - Psi Phi(dt)
+
+(the GPMP "GP interpolation").  For this prior Q_c cancels and so does the prior mean: per degree of freedom the weights are
+the cubic Hermite basis on (q, v), which is what `hermite_weights` returns.  The reference has no counterpart.
+"""
+import numpy as np
+
+
+def fine_length(T, n_sub):
+    """Number of fine states of a T-waypoint trajectory with n_sub states inserted per interval."""
+    T, n_sub = int(T), int(n_sub)
+    if T < 2 or n_sub < 0:
+        raise ValueError("fine_length: T >= 2 and n_sub >= 0")
+    return (T - 1) * (n_sub + 1) + 1
+
+
+def fine_times(T, n_sub, dt):
+    """Time of every fine state [T_f]: fine index f = i (n_sub + 1) + m lies at (i + m / (n_sub + 1)) dt."""
+    f = np.arange(fine_length(T, n_sub), dtype=np.float64)
+    return f * (float(dt) / (n_sub + 1))
+
+
+def hermite_weights(n_sub, dt):
+    """(Lambda, Psi), each [n_sub + 1, 2, 2]: the 2 x 2 blocks, per degree of freedom on (q, v), of the interpolation weights
+    at s = m / (n_sub + 1), m = 0 .. n_sub, of an interval of length dt; x(s) = Lambda[m] x_i + Psi[m] x_{i+1}.
+    m = 0 is the support state itself: Lambda[0] = I, Psi[0] = 0."""
+    n_sub, dt = int(n_sub), float(dt)
+    if n_sub < 0 or not dt > 0.:
+        raise ValueError("hermite_weights: n_sub >= 0 and dt > 0")
+    s = np.arange(n_sub + 1, dtype=np.float64) / (n_sub + 1)
+    s2, s3 = s * s, s * s * s
+    h00, h10, h01, h11 = 2 * s3 - 3 * s2 + 1, s3 - 2 * s2 + s, -2 * s3 + 3 * s2, s3 - s2
+    g00, g10, g11 = 6 * s2 - 6 * s, 3 * s2 - 4 * s + 1, 3 * s2 - 2 * s
+    lam = np.empty((n_sub + 1, 2, 2))
+    psi = np.empty((n_sub + 1, 2, 2))
+    lam[:, 0, 0], lam[:, 0, 1], lam[:, 1, 0], lam[:, 1, 1] = h00, h10 * dt, g00 / dt, g10
+    psi[:, 0, 0], psi[:, 0, 1], psi[:, 1, 0], psi[:, 1, 1] = h01, h11 * dt, -g00 / dt, g11
+    return lam, psi
+
+
+def interpolate(trajs, n_sub, dt):
+    """The same interpolation on the host, in the dtype of `trajs` [..., T, 2n] -> [..., T_f, 2n] (checks, plots)."""
+    x = np.asarray(trajs)
+    T, n = x.shape[-2], x.shape[-1] // 2
+    lam, psi = hermite_weights(n_sub, dt)
+    k1 = n_sub + 1
+    out = np.empty(x.shape[:-2] + (fine_length(T, n_sub), 2 * n), dtype=x.dtype)
+    a, b = x[..., :-1, :], x[..., 1:, :]
+    for m in range(k1):
+        la, ps = lam[m], psi[m]
+        q = la[0, 0] * a[..., :n] + la[0, 1] * a[..., n:] + ps[0, 0] * b[..., :n] + ps[0, 1] * b[..., n:]
+        v = la[1, 0] * a[..., :n] + la[1, 1] * a[..., n:] + ps[1, 0] * b[..., :n] + ps[1, 1] * b[..., n:]
+        out[..., m:-1:k1, :n], out[..., m:-1:k1, n:] = q, v
+    out[..., 0:-1:k1, :] = a                      # support states are copies
+    out[..., -1, :] = x[..., -1, :]
+    return out

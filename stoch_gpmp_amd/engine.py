@@ -550,6 +550,47 @@ class Engine:
                                               L.ptr(value), L.ptr(grad), L.stream_ptr()))
         return value, grad
 
+    # ------------------------------------------------------------------ dense trajectories
+    def interpolate(self, trajs, n_sub, dt):
+        """GP interpolation of trajs [B,T,d] with `n_sub` states inserted per interval -> [B,T_f,d], T_f = (T-1)(n_sub+1)+1
+        (include/sgpmp.h: sgpmp_interpolate; host-side twin of the weights: stoch_gpmp_amd/dense.py)."""
+        self._chk(trajs, "trajs")
+        B = trajs.numel() // (self.T * self.d)
+        n_sub = int(n_sub)
+        k = min(max(n_sub, 0), L.MAX_SUBSTEPS)           # (an n_sub out of range is the library's to refuse)
+        out = torch.empty(B, (self.T - 1) * (k + 1) + 1, self.d, **self.tensor_args)
+        with torch.cuda.device(self.device):
+            L.check(self.lib.sgpmp_interpolate(self._ctx, L.ptr(trajs), B, n_sub, float(dt), L.ptr(out), L.stream_ptr()))
+        return out
+
+    def validate(self, trajs, n_sub, dt, spheres=None, grid_term=-1, q_limits=None, v_limits=None):
+        """Check of ALL fine states of trajs [B,T,d] -> (values [B,4], where [B,4] int32): obstacle clearance, self-clearance,
+        limit excess, grid occupancy and the first fine index attaining each (include/sgpmp.h: sgpmp_validate).
+        q_limits = (lower [n], upper [n]); v_limits = [n] (symmetric)."""
+        self._chk(trajs, "trajs")
+        B = trajs.numel() // (self.T * self.d)
+        n_sph = 0
+        if spheres is not None:
+            spheres = spheres.reshape(-1, 4)
+            self._chk(spheres, "obstacle_spheres")
+            n_sph = spheres.shape[0]
+
+        def host(v):
+            if v is None:
+                return None
+            vals = [float(x) for x in torch.as_tensor(v, dtype=torch.float64).flatten()]
+            if len(vals) != self.n:
+                raise ValueError(f"limits: expected {self.n} numbers, got {len(vals)}")
+            return (C.c_double * self.n)(*vals)
+        q_lo, q_hi = (None, None) if q_limits is None else (host(q_limits[0]), host(q_limits[1]))
+        v_max = host(v_limits)
+        values = torch.empty(B, 4, **self.tensor_args)
+        where = torch.empty(B, 4, device=self.device, dtype=torch.int32)
+        with torch.cuda.device(self.device):
+            L.check(self.lib.sgpmp_validate(self._ctx, L.ptr(trajs), B, int(n_sub), float(dt), L.ptr(spheres), n_sph,
+                                            int(grid_term), q_lo, q_hi, v_max, L.ptr(values), L.ptr(where), L.stream_ptr()))
+        return values, where
+
     # ------------------------------------------------------------------ GPMP (Gauss-Newton planner)
     def gpmp_linearize(self, means, spheres=None, diag_sum=None):
         """Fields + Jacobians of the cost list at the particle means; optionally the local sum of the

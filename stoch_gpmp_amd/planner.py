@@ -66,6 +66,30 @@ from .engine import Engine
 _UNSEEDED = itertools.count()
 
 
+class TrajectoryValidity:
+    """Result of StochGPMP.validate_trajectories: per trajectory, over all fine states of its GP interpolation,
+    `clearance` (min link-to-sphere distance), `self_clearance` (min distance of the link pairs that move against each other),
+    `limit_excess` (max violation of the joint / velocity limits, <= 0: inside), `occupancy` (max grid value), `where` [B,4]
+    (the first fine index attaining each, -1: column not evaluated) and `valid`.  A column whose inputs were absent holds
+    +-inf and does not constrain; a trajectory with a non-finite state holds NaN everywhere and is not valid."""
+
+    def __init__(self, values, where, n_sub, buffer, self_buffer):
+        self.values, self.where, self.n_sub = values, where, n_sub
+        self.buffer, self.self_buffer = buffer, self_buffer
+        self.clearance, self.self_clearance = values[:, 0], values[:, 1]
+        self.limit_excess, self.occupancy = values[:, 2], values[:, 3]
+        self.valid = (self.clearance > buffer) & (self.self_clearance > self_buffer) \
+            & (self.limit_excess <= 0) & (self.occupancy <= 0)
+
+
+class BestTrajectories:
+    """Result of StochGPMP.best_trajectories: per goal the global `index` of the lowest-cost valid particle (-1: none),
+    its `cost` (inf: none), its dense trajectory `trajectories` [G,T_f,d] (NaN: none), and the `validity` of all particles."""
+
+    def __init__(self, index, cost, trajectories, validity, costs):
+        self.index, self.cost, self.trajectories, self.validity, self.costs = index, cost, trajectories, validity, costs
+
+
 class StochGPMP:
     _discard_draw_at_reset = True
 
@@ -683,6 +707,66 @@ class StochGPMP:
         elif mode == 'mean':
             return self._mean.clone()
         raise ValueError('Unidentified sampling mode in get_next_action')
+
+    # ------------------------------------------------------------------------------- dense trajectories
+    # (no reference counterpart: the reference checks the support waypoints only and picks `best` by weight alone)
+    def _dense_input(self, trajs):
+        T, d = self.traj_len, self.d_state_opt
+        if trajs is None:
+            trajs = self.particle_means
+        trajs = trajs.to(**self.tensor_args).reshape(-1, T, d)
+        return trajs if trajs.is_contiguous() else trajs.contiguous()
+
+    def interpolate_trajectories(self, trajs=None, n_sub=4):
+        """GP interpolation (the posterior mean of the planner's constant-velocity prior between support states) of
+        trajs [B,T,d] (default: this rank's particle means) -> [B,T_f,d], T_f = (T-1)(n_sub+1)+1  (stoch_gpmp_amd/dense.py)."""
+        return self._engine.interpolate(self._dense_input(trajs), n_sub, self.dt)
+
+    def _grid_term(self):
+        if not self._native_cost:
+            return -1
+        for i, dsc in enumerate(self.cost.descriptors()):
+            if dsc["kind"] == L.COST_GRID:
+                return i
+        return -1
+
+    def validate_trajectories(self, trajs=None, n_sub=4, buffer=0., self_buffer=0., q_limits=None, v_limits=None,
+                              **observation):
+        """Which trajectories could a robot execute?  Every fine state of the interpolated trajectories (never written to
+        memory: one fused launch, csrc/traj_dense.hip) against the obstacle spheres of `observation`, the robot's own links,
+        the joint limits q_limits = (lower, upper) / velocity limits v_limits and the cost list's occupancy grid.
+        -> TrajectoryValidity."""
+        if self._native_cost and self._cost_version != self.cost.version():
+            self.cost.compile_into(self._engine)
+            self._cost_version = self.cost.version()
+        has_chain = self._native_cost and getattr(self.cost, "chain", None) is not None
+        spheres = self._spheres(observation) if has_chain else None
+        values, where = self._engine.validate(self._dense_input(trajs), n_sub, self.dt, spheres=spheres,
+                                              grid_term=self._grid_term(), q_limits=q_limits, v_limits=v_limits)
+        return TrajectoryValidity(values, where, n_sub, buffer, self_buffer)
+
+    def best_trajectories(self, n_sub=4, buffer=0., self_buffer=0., q_limits=None, v_limits=None, **observation):
+        """Per goal, the lowest-cost particle among those that pass validate_trajectories: all particles of all ranks
+        (gather_particle_means), each scored by the cost program (CostComposite.eval on its mean).  -> BestTrajectories."""
+        means = self.gather_particle_means()
+        G, nppg, S = self.num_goals, self.num_particles_per_goal, self.num_samples
+        val = self.validate_trajectories(means, n_sub=n_sub, buffer=buffer, self_buffer=self_buffer, q_limits=q_limits,
+                                         v_limits=v_limits, **observation)
+        if self._native_cost:
+            costs = torch.empty(G * nppg, **self.tensor_args)
+            sph = self._spheres(observation)
+            for g in range(G):                               # (row offset g nppg S: the goal prior looks goal g up)
+                self._engine.cost_eval(means[g * nppg:(g + 1) * nppg], batch_offset=g * nppg * S, spheres=sph,
+                                       out=costs[g * nppg:(g + 1) * nppg])
+        else:
+            costs = self.cost.eval(means, **observation).reshape(-1).to(**self.tensor_args)
+        masked = torch.where(val.valid, costs, torch.full_like(costs, float('inf'))).reshape(G, nppg)
+        cost, k = masked.min(dim=1)
+        found = torch.isfinite(cost)
+        index = torch.where(found, k + torch.arange(G, device=k.device) * nppg, torch.full_like(k, -1))
+        dense = self.interpolate_trajectories(means[index.clamp(min=0)], n_sub=n_sub)
+        dense = torch.where(found.reshape(G, 1, 1), dense, torch.full_like(dense, float('nan')))
+        return BestTrajectories(index, cost, dense, val, costs)
 
     def get_recent_samples(self):
         return (self._recent_state_trajectories.detach().clone(),

@@ -14,6 +14,12 @@ from ..engine import Engine
 
 from .panda_chain import PANDA_CHAIN, PANDA_LINK_NAMES, PANDA_Q_LOWER, PANDA_Q_UPPER  # noqa: F401
 
+# Joint limits of the seven revolute joints as data, typed from the <limit .../> elements of the same URDF
+# (panda_arm_no_gripper.urdf:47,72,97,122,147,172,197): positions `lower` / `upper` [rad], `velocity` [rad/s].
+PANDA_Q_LIMITS = ((-2.8973, -1.7628, -2.8973, -3.0718, -2.8973, -0.0175, -2.8973),
+                  (2.8973, 1.7628, 2.8973, -0.0698, 2.8973, 3.7525, 2.8973))
+PANDA_V_LIMITS = (2.1750, 2.1750, 2.1750, 2.1750, 2.6100, 2.6100, 2.6100)
+
 
 class URDFChain:
     """A serial chain of revolute(z)/fixed joints; FK runs in the HIP kernel `fk_frames_kernel`."""
