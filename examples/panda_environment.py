@@ -6,7 +6,11 @@ headless.  Two things the reference gets from libraries that are not available h
 fixed data: the goal joint configuration (PyBullet IK in the reference, lines 55-62) is a constant
 inside the joint limits, and the end-effector target frame is the FK of that configuration.
 
-    python examples/panda_environment.py [--iters 500] [--seed 0]
+    python examples/panda_environment.py [--iters 500] [--seed 0] [--dense-cost]
+
+--dense-cost plans twice from the same seed: as the reference does, and with the continuous-time term switched on (collision
+terms on 4 GP-interpolated states per interval, the Panda's joint and velocity limits as a penalty on all fine states), and
+prints the best valid particle of each.
 """
 import argparse
 import os
@@ -28,11 +32,19 @@ from stoch_gpmp_amd.robots.panda import PANDA_Q_LIMITS, PANDA_V_LIMITS, Differen
 
 
 def main(opt_iters=500, seed=None, num_particles_per_goal=5, num_samples=32, num_obst=5, traj_len=64,
-         dtype=torch.float32, verbose=True):
+         dtype=torch.float32, verbose=True, dense_cost=False):
+    seed = int(time.time()) if seed is None else seed
+    if not dense_cost:
+        return plan(opt_iters, seed, num_particles_per_goal, num_samples, num_obst, traj_len, dtype, verbose, None)
+    plan(opt_iters, seed, num_particles_per_goal, num_samples, num_obst, traj_len, dtype, verbose, None)
+    setting = dict(n_sub=4, weight=1.0, q_limits=PANDA_Q_LIMITS, v_limits=PANDA_V_LIMITS, sigma_limit=0.01)
+    return plan(opt_iters, seed, num_particles_per_goal, num_samples, num_obst, traj_len, dtype, verbose, setting)
+
+
+def plan(opt_iters, seed, num_particles_per_goal, num_samples, num_obst, traj_len, dtype, verbose, dense_cost):
     device = torch.device('cuda:0')
     tensor_args = {'device': device, 'dtype': dtype}
     dt = 0.05
-    seed = int(time.time()) if seed is None else seed
     random.seed(seed)
     np.random.seed(seed)
     torch.manual_seed(seed)
@@ -63,7 +75,7 @@ def main(opt_iters=500, seed=None, num_particles_per_goal=5, num_samples=32, num
         multi_goal_states=multi_goal_states, cost=cost, step_size=0.1,
         sigma_start_init=0.0001, sigma_goal_init=0.1, sigma_gp_init=0.8,
         sigma_start_sample=0.001, sigma_goal_sample=0.07, sigma_gp_sample=0.1, seed=seed,
-        tensor_args=tensor_args)
+        tensor_args=tensor_args, dense_cost=dense_cost)
 
     # spawn obstacles (reference lines 124-133)
     obstacle_spheres = np.zeros((1, num_obst, 4))
@@ -81,6 +93,7 @@ def main(opt_iters=500, seed=None, num_particles_per_goal=5, num_samples=32, num
             print_info(i, opt_iters, t_iter, start_time, costs)
     torch.cuda.synchronize()
     if verbose:
+        print("continuous-time cost " + ("off" if dense_cost is None else f"on (n_sub = {dense_cost['n_sub']}, Panda limits)"))
         print(f"{opt_iters + 1} iterations in {time.time() - start_time:.3f} s")
         ee = panda_fk.compute_forward_kinematics_all_links(planner.particle_means[:, -1, :n_dof].contiguous())[:, -1, :3, 3]
         print("end-effector distance to target per particle [m]:",
@@ -101,5 +114,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=500)
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--dense-cost", action="store_true",
+                    help="plan a second time with the collision / limit cost on the GP-interpolated states and compare")
     a = ap.parse_args()
-    main(opt_iters=a.iters, seed=a.seed)
+    main(opt_iters=a.iters, seed=a.seed, dense_cost=a.dense_cost)

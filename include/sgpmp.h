@@ -477,6 +477,34 @@ int sgpmp_validate(sgpmp_ctx* ctx, const void* trajs, int64_t batch, int n_sub, 
                    const double* v_max,                     /* HOST [n_dof] or NULL          */
                    void* values, int32_t* where, void* stream);
 
+/* Continuous-time collision and limit cost of trajs [B,T,d] on the fine states of sgpmp_interpolate (same device function, same
+ * bits), per trajectory b:
+ *   dense[b] = weight * sum over the INSERTED states (m = 1 .. n_sub of every interval) of sum over the GRID / SPHERES / SELF terms
+ *                       of the cost program of K_term * field_term(x_f)
+ *            + 1/sigma_limit^2 * sum over ALL fine states f and dof k of
+ *                       max(0, q_lo[k] - q)^2 + max(0, q - q_hi[k])^2 + max(0, |q'| - v_max[k])^2
+ * The support states' collision cost stays with the sweep: sgpmp_cost_eval + sgpmp_dense_cost counts every fine state once.  The
+ * fields are the sweep's own (grid value at (q_0, q_1); rbf / sdf / clamped sdf / occupancy sphere fields with a term's
+ * interpolated link points; the full L x L self field); GP, goal-prior and end-effector terms are ignored, and so is the option
+ * f64_fields_f32.  A limit that is not given (NULL; one side of q_lo / q_hi alone is allowed) contributes nothing; a SPHERES term
+ * with n_spheres = 0 contributes nothing; weight = 0 leaves the limit part.  A trajectory with any non-finite fine state reports
+ * NaN.  accumulate = 0 writes, 1 adds to what the outputs hold (both given: costs64 is the accumulator, costs its rounding);
+ * each lane sums its interval in the ctx dtype, the sum over the lanes and the add are in double.
+ * Chains the library was built with (Panda, no interpolated link points) run register-resident generated code, every other
+ * chain the generic forward kinematics through LDS; sgpmp_last_dense_kernel names the kernel of this thread's last launch.
+ * SGPMP_EINVAL: n_sub outside [0, SGPMP_MAX_SUBSTEPS], dt <= 0, weight < 0, a limit with sigma_limit <= 0, and with batch > 0 a
+ * null trajs or both outputs null; SGPMP_ESTATE: a SPHERES / SELF term without a chain, a SPHERES term with n_spheres > 0 and
+ * spheres NULL.  batch = 0 is a no-op. */
+int sgpmp_dense_cost(sgpmp_ctx* ctx, const void* trajs, int64_t batch, int n_sub, double dt,
+                     const void* spheres, int n_spheres,          /* DEVICE [n,4] or NULL */
+                     double weight,                               /* scales the collision part */
+                     const double* q_lo, const double* q_hi,      /* HOST [n_dof] or NULL */
+                     const double* v_max, double sigma_limit,     /* HOST [n_dof] or NULL; > 0 when any limit is given */
+                     int accumulate,                              /* 0: write, 1: add to what is there */
+                     void* costs, double* costs64,                /* [B] ctx dtype / double; either may be NULL */
+                     void* stream);
+const char* sgpmp_last_dense_kernel(void);   /* thread-local static name of the kernel the last call launched; "" before */
+
 /* ---- GPMP: the reference's Gauss-Newton planner (planner.py:352-661) ------- */
 /* First half of GPMP._step (planner.py:580-581, cost.get_linear_system): evaluates every smooth link
  * field of the cost list and its Jacobian at waypoints 1..T-1 of the particle means [P,T,d] (kept in

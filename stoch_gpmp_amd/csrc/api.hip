@@ -949,6 +949,7 @@ int sgpmp_ctx_view(sgpmp_ctx* c, SgpmpCtxView* out) {
     out->h_chain = &c->h_chain;
     out->d_chain = c->d_chain;
     out->pair_mask = c->pair_mask;
+    out->tg = &c->tg;
     if (!c->have_costs) return SGPMP_OK;
     const int rc = finalize_program(c);
     if (rc == SGPMP_OK) out->prog = &c->h_prog;

@@ -167,6 +167,7 @@ struct SgpmpCtxView {
     const ChainDev* d_chain;      // DEVICE copy
     const CostProgram* prog;      // HOST, finalized (point counts resolved, pushed to the device); null: no cost program set
     const uint32_t* pair_mask;    // [SGPMP_MAX_LINKS] bit j of word i: links i - j >= 2 whose distance depends on q
+    const SgpmpToggles* tg;       // the context's development switches (the ones launch_cost picks its kernel by)
 };
 // fills *out; runs finalize_program when costs are set and returns its status (out->prog stays null when it fails)
 int sgpmp_ctx_view(sgpmp_ctx* c, SgpmpCtxView* out);

@@ -25,6 +25,7 @@
 #include "chain_code_generated.h"
 #include "sgpmp_internal.h"
 #include "cost_device.h"
+#include "cost_host.h"
 
 // ---------------------------------------------------------------------------------- shared Hermite evaluation
 template <typename real>
@@ -420,4 +421,262 @@ extern "C" int sgpmp_validate(sgpmp_ctx* c, const void* trajs, int64_t batch, in
         : launch_validate<float>(v, trajs, batch, n_sub, dt, spheres, n_spheres, grid, q_lo, q_hi, v_max, values, where,
                                  (hipStream_t)stream);
     return e == hipSuccess ? SGPMP_OK : dense_hip_error("sgpmp_validate", e);
+}
+
+// ---------------------------------------------------------------------------------- sgpmp_dense_cost
+// The collision terms of the cost program on the INSERTED fine states (the support states stay with the sweep) and a quadratic
+// joint / velocity limit penalty on ALL fine states, summed per trajectory.  validate_kernel's mapping -- one wave per
+// trajectory, one lane per support waypoint, the lane walks its interval -- and the same hermite_state; each lane sums its
+// states in the compute type, the wave sum and the add into what `costs64` holds are in double.  Three instantiations:
+//   MODE 2  built-in Panda code: fk_cg / spheres_field_cg / self_field_cg in registers, the sphere terms of the links that
+//           never move once per wave (an LDS word per term) -- the sweep's FKMODE 1000 code, picked by launch_cost's conditions;
+//   MODE 1  generic: any chain, interpolated points; link positions in one LDS column per lane (fk_points_const, add_interp_points,
+//           spheres_field, self_field), as in validate_kernel;
+//   MODE 0  no link field (planar GRID programs, limits only): no LDS.
+template <typename real>
+struct DenseCostK {
+    int T, n_sub;
+    const ChainDev* chain;            // DEVICE (MODE 1), or null
+    int n_links;
+    const real* spheres;              // DEVICE [n_spheres][4], or null
+    int n_spheres;
+    int n_terms;                      // GRID / SPHERES / SELF terms of the cost program, in program order
+    int has_qlim, has_vlim, accumulate;
+    real weight, inv_sigma2;
+    real q_lo[SGPMP_MAX_DOF], q_hi[SGPMP_MAX_DOF], v_max[SGPMP_MAX_DOF];
+    TermK<real> t[SGPMP_MAX_TERMS];
+};
+// (HIP passes at most 4 KiB of kernel arguments)
+static_assert(sizeof(DenseCostK<double>) + sizeof(HermiteK<double>) + 4 * sizeof(void*) <= 4096, "dense_cost_kernel: kernel arguments");
+
+template <typename real, int N, int MODE>
+__global__ void __launch_bounds__(64)
+dense_cost_kernel(const real* __restrict__ trajs, long long batch, DenseCostK<real> A, HermiteK<real> H, real* __restrict__ costs,
+                  double* __restrict__ costs64) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const int lane = threadIdx.x;
+    const int T = A.T, k1 = A.n_sub + 1;
+    const real big = std::numeric_limits<real>::max();
+    __shared__ real stat[MODE == 2 ? SGPMP_MAX_TERMS : 1];     // MODE 2: sphere terms of the static links
+    // Once per BLOCK, outside the trajectory loop: the static links and their sphere terms do not depend on the trajectory.  The
+    // cost (one forward kinematics and the spheres x static links on all 64 lanes) is amortised only over the trajectories
+    // this block serves -- ONE while dense_blocks hands out a block per trajectory (batch < 2^20); it is part of the call's
+    // fixed time.  Whoever gives a block several trajectories gets it cheaper, not wrong.
+    if constexpr (MODE == 2) {
+        using CC = ChainCode_panda;
+        real q0[CC::N], P0[CC::NREP][3];
+#pragma unroll
+        for (int k = 0; k < CC::N; ++k) q0[k] = 0;
+        fk_cg<real, CC>(q0, P0);                               // static links do not depend on q
+        for (int ti = 0; ti < A.n_terms; ++ti) {
+            const TermK<real>& tm = A.t[ti];
+            if (tm.kind != SGPMP_COST_SPHERES) continue;
+            const real init = ((tm.flags & 15) == SGPMP_FIELD_SDF) ? (real)-1e30 : (real)0;
+            const real v = spheres_field_cg<real, CC, true>(tm, P0, A.spheres, A.n_spheres, init);
+            if (lane == 0) stat[ti] = v;
+        }
+        __syncthreads();
+    }
+    for (long long b = blockIdx.x; b < batch; b += gridDim.x) {
+        const real* tr = trajs + (size_t)b * T * (2 * N);
+        real part = 0, lim = 0;
+        bool bad = false;
+        for (int base = 0; base < T; base += 64) {
+            const int i = base + lane;
+            real a[2 * N], nb[2 * N], x[2 * N];
+            load_interval<real, N>(tr, T, i, lane, a, nb);
+            const int nm = i < T - 1 ? k1 : (i == T - 1 ? 1 : 0);
+            for (int m = 0; m < nm; ++m) {
+                if (m == 0) {
+#pragma unroll
+                    for (int k = 0; k < 2 * N; ++k) x[k] = a[k];
+                } else {
+                    hermite_state<real, N>(a, nb, H.c[m - 1], x);
+                }
+                // explicit test: fmin / fmax drop a NaN, comparisons with one are all false
+                bool finite = true;
+#pragma unroll
+                for (int k = 0; k < 2 * N; ++k) finite = finite && (fabs(x[k]) <= big);
+                if (!finite) { bad = true; continue; }
+                if (A.has_qlim | A.has_vlim) {
+#pragma unroll
+                    for (int k = 0; k < N; ++k) {
+                        if (A.has_qlim) {
+                            const real lo = A.q_lo[k] - x[k], hi = x[k] - A.q_hi[k];
+                            if (lo > 0) lim += lo * lo;
+                            if (hi > 0) lim += hi * hi;
+                        }
+                        if (A.has_vlim) {
+                            const real ve = fabs(x[N + k]) - A.v_max[k];
+                            if (ve > 0) lim += ve * ve;
+                        }
+                    }
+                }
+                if (m == 0) continue;                          // a support state: its collision cost is the sweep's
+                if constexpr (MODE == 2) {
+                    using CC = ChainCode_panda;
+                    real q[N], Pq[CC::NREP][3];
+#pragma unroll
+                    for (int k = 0; k < N; ++k) q[k] = x[k];
+                    fk_cg<real, CC>(q, Pq);
+                    for (int ti = 0; ti < A.n_terms; ++ti) {
+                        const TermK<real>& tm = A.t[ti];
+                        real f;
+                        if (tm.kind == SGPMP_COST_SPHERES)
+                            f = spheres_field_cg<real, CC, false>(tm, Pq, A.spheres, A.n_spheres, stat[ti]);
+                        else if (tm.kind == SGPMP_COST_SELF)
+                            f = self_field_cg<real, CC>(tm, Pq);
+                        else
+                            f = grid_value<real>(tm, x[0], x[N > 1 ? 1 : 0]);
+                        part += tm.K * f;
+                    }
+                } else {
+                    if constexpr (MODE == 1) {
+                        real* col = reinterpret_cast<real*>(lds_raw) + lane;   // this lane's column of points (SoA, stride 64)
+                        real q[N];
+#pragma unroll
+                        for (int k = 0; k < N; ++k) q[k] = x[k];
+                        fk_points_const<real, N>(as_const(A.chain), A.n_links, q, col);
+                        for (int ti = 0; ti < A.n_terms; ++ti) {
+                            const TermK<real>& tm = A.t[ti];
+                            if (tm.kind == SGPMP_COST_GRID) continue;
+                            if (tm.n_interp > 0) add_interp_points<real>(tm, A.n_links, col, 64);
+                            const real f = tm.kind == SGPMP_COST_SPHERES
+                                ? spheres_field<real>(tm, tm.n_points, col, 64, A.spheres, A.n_spheres)
+                                : self_field<real>(tm, tm.n_points, col, 64);
+                            part += tm.K * f;
+                        }
+                    }
+                    for (int ti = 0; ti < A.n_terms; ++ti) {
+                        const TermK<real>& tm = A.t[ti];
+                        if (tm.kind == SGPMP_COST_GRID) part += tm.K * grid_value<real>(tm, x[0], x[N > 1 ? 1 : 0]);
+                    }
+                }
+            }
+        }
+        double acc = wave_sum((double)(A.weight * part) + (double)(A.inv_sigma2 * lim));
+        const bool any_bad = __any(bad ? 1 : 0) != 0;
+        if (lane == 0) {
+            if (any_bad) acc = std::numeric_limits<double>::quiet_NaN();
+            if (A.accumulate) acc += costs64 ? costs64[b] : (double)costs[b];   // (both given: costs64 is the accumulator, costs its rounding)
+            if (costs64) costs64[b] = acc;
+            if (costs) costs[b] = (real)acc;
+        }
+    }
+}
+
+static thread_local const char* g_last_dense_kernel = "";
+extern "C" const char* sgpmp_last_dense_kernel(void) { return g_last_dense_kernel; }
+
+template <typename real>
+static hipError_t launch_dense_cost(const SgpmpCtxView& v, const void* trajs, long long batch, int n_sub, double dt,
+                                    const void* spheres, int n_spheres, double weight, const double* q_lo, const double* q_hi,
+                                    const double* v_max, double sigma_limit, int accumulate, void* costs, double* costs64,
+                                    hipStream_t stream) {
+    constexpr bool f64 = sizeof(real) == 8;
+    const char* name = "";
+    // the name is published only once the launch has been accepted
+    auto launched = [&]() { const hipError_t e = hipGetLastError(); if (e == hipSuccess) g_last_dense_kernel = name; return e; };
+    const int n = v.dims.n_dof;
+    DenseCostK<real> A;
+    std::memset(&A, 0, sizeof(A));
+    A.T = v.dims.traj_len; A.n_sub = n_sub; A.accumulate = accumulate ? 1 : 0;
+    A.weight = (real)weight;
+    bool fk = false, interp = false;
+    int max_pts = 0;
+    // weight 0 (the limit part alone) and n_sub 0 (no inserted state) evaluate no field at all
+    for (int i = 0; v.prog && weight > 0. && n_sub > 0 && i < v.prog->n_terms; ++i) {
+        const CostTerm& s = v.prog->terms[i];
+        if (s.kind == SGPMP_COST_SPHERES && n_spheres < 1) continue;       // no obstacle: the term adds nothing
+        if (s.kind != SGPMP_COST_GRID && s.kind != SGPMP_COST_SPHERES && s.kind != SGPMP_COST_SELF) continue;
+        A.t[A.n_terms++] = make_termk<real>(s);
+        if (s.kind != SGPMP_COST_GRID) {
+            fk = true;
+            interp = interp || s.n_interp > 0;
+            max_pts = s.n_points > max_pts ? s.n_points : max_pts;
+        }
+    }
+    const real inf = std::numeric_limits<real>::infinity();
+    A.has_qlim = (q_lo || q_hi) ? 1 : 0;
+    A.has_vlim = v_max ? 1 : 0;
+    A.inv_sigma2 = (A.has_qlim | A.has_vlim) ? (real)(1. / (sigma_limit * sigma_limit)) : (real)0;
+    for (int k = 0; k < SGPMP_MAX_DOF; ++k) {                  // a one-sided position limit: the other side never binds
+        A.q_lo[k] = (q_lo && k < n) ? (real)q_lo[k] : -inf;
+        A.q_hi[k] = (q_hi && k < n) ? (real)q_hi[k] : inf;
+        A.v_max[k] = (v_max && k < n) ? (real)v_max[k] : inf;
+    }
+    const HermiteK<real> H = hermite_coefs<real>(n_sub, dt);
+    const dim3 grid(dense_blocks(batch)), block(64);
+    if (fk) {
+        A.spheres = n_spheres > 0 ? (const real*)spheres : nullptr;
+        A.n_spheres = A.spheres ? n_spheres : 0;
+        A.n_links = v.h_chain->n_links;
+        // launch_cost's conditions for the code built with the library
+        const FkPlan& plan = v.h_chain->plan;
+        const bool cg = plan.fast && plan.codegen_id == 1 && n == ChainCode_panda::N && !interp && !v.tg->force_generic_fk &&
+                        !v.tg->no_chain_codegen;
+        if (cg) {
+            name = f64 ? "dense_cost_kernel<f64, generated chain>" : "dense_cost_kernel<f32, generated chain>";
+            hipLaunchKernelGGL((dense_cost_kernel<real, ChainCode_panda::N, 2>), grid, block, 0, stream, (const real*)trajs,
+                               batch, A, H, (real*)costs, costs64);
+            return launched();
+        }
+        A.chain = v.d_chain;
+        if (max_pts < A.n_links) max_pts = A.n_links;
+        // finalize_program admits at most SGPMP_MAX_POINTS points per term: the columns take at most 48 KB
+        static_assert((size_t)SGPMP_MAX_POINTS * 3 * 64 * sizeof(double) <= 48 * 1024, "dense_cost_kernel: LDS columns");
+        if (max_pts > SGPMP_MAX_POINTS) return hipErrorInvalidValue;
+        const size_t lds = (size_t)max_pts * 3 * 64 * sizeof(real);
+        name = f64 ? "dense_cost_kernel<f64, generic FK>" : "dense_cost_kernel<f32, generic FK>";
+#define DENSE_CASE(NN)                                                                                               \
+    case NN:                                                                                                         \
+        hipLaunchKernelGGL((dense_cost_kernel<real, NN, 1>), grid, block, lds, stream, (const real*)trajs, batch, A, \
+                           H, (real*)costs, costs64);                                                                \
+        break;
+        switch (n) {
+            DENSE_CASE(1) DENSE_CASE(2) DENSE_CASE(3) DENSE_CASE(4) DENSE_CASE(5) DENSE_CASE(6) DENSE_CASE(7) DENSE_CASE(8)
+            default: return hipErrorInvalidValue;
+        }
+#undef DENSE_CASE
+        return launched();
+    }
+    name = f64 ? "dense_cost_kernel<f64, no FK>" : "dense_cost_kernel<f32, no FK>";
+#define DENSE_CASE(NN)                                                                                               \
+    case NN:                                                                                                         \
+        hipLaunchKernelGGL((dense_cost_kernel<real, NN, 0>), grid, block, 0, stream, (const real*)trajs, batch, A,   \
+                           H, (real*)costs, costs64);                                                                \
+        break;
+    switch (n) {
+        DENSE_CASE(1) DENSE_CASE(2) DENSE_CASE(3) DENSE_CASE(4) DENSE_CASE(5) DENSE_CASE(6) DENSE_CASE(7) DENSE_CASE(8)
+        default: return hipErrorInvalidValue;
+    }
+#undef DENSE_CASE
+    return launched();
+}
+
+extern "C" int sgpmp_dense_cost(sgpmp_ctx* c, const void* trajs, int64_t batch, int n_sub, double dt, const void* spheres,
+                                int n_spheres, double weight, const double* q_lo, const double* q_hi, const double* v_max,
+                                double sigma_limit, int accumulate, void* costs, double* costs64, void* stream) {
+    const bool limits = q_lo || q_hi || v_max;
+    if (!c || batch < 0 || n_sub < 0 || n_sub > SGPMP_MAX_SUBSTEPS || !(dt > 0.) || !(weight >= 0.) || n_spheres < 0 ||
+        (limits && !(sigma_limit > 0.)) || (batch > 0 && (!trajs || (!costs && !costs64))))
+        return sgpmp_set_error(SGPMP_EINVAL, "sgpmp_dense_cost: bad argument (n_sub in [0, 31], dt > 0, weight >= 0, "
+                                             "sigma_limit > 0 with limits, non-null trajs and one output)");
+    SgpmpCtxView v;
+    const int view_rc = sgpmp_ctx_view(c, &v);
+    if (view_rc != SGPMP_OK) return view_rc;                   // (finalize_program said why)
+    for (int i = 0; v.prog && i < v.prog->n_terms; ++i) {
+        const int kind = v.prog->terms[i].kind;
+        if ((kind == SGPMP_COST_SPHERES || kind == SGPMP_COST_SELF) && !v.have_chain)
+            return sgpmp_set_error(SGPMP_ESTATE, "sgpmp_dense_cost: link-field terms need an FK chain (sgpmp_set_fk)");
+        if (kind == SGPMP_COST_SPHERES && n_spheres > 0 && !spheres)
+            return sgpmp_set_error(SGPMP_ESTATE, "sgpmp_dense_cost: n_spheres > 0 without obstacle spheres");
+    }
+    if (batch == 0) return SGPMP_OK;
+    const hipError_t e = v.dims.dtype == SGPMP_F64
+        ? launch_dense_cost<double>(v, trajs, batch, n_sub, dt, spheres, n_spheres, weight, q_lo, q_hi, v_max, sigma_limit,
+                                    accumulate, costs, costs64, (hipStream_t)stream)
+        : launch_dense_cost<float>(v, trajs, batch, n_sub, dt, spheres, n_spheres, weight, q_lo, q_hi, v_max, sigma_limit,
+                                   accumulate, costs, costs64, (hipStream_t)stream);
+    return e == hipSuccess ? SGPMP_OK : dense_hip_error("sgpmp_dense_cost", e);
 }

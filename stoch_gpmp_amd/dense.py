@@ -1,5 +1,5 @@
 """Host-side arithmetic of the dense (GP-interpolated) trajectories: index bookkeeping and the interpolation weights that
-`sgpmp_interpolate` / `sgpmp_validate` (csrc/traj_dense.hip) apply on the GPU.  numpy only, no GPU, no library.
+`sgpmp_interpolate` / `sgpmp_validate` / `sgpmp_dense_cost` (csrc/traj_dense.hip) apply on the GPU.  numpy only, no GPU, no library.
 
 Between two support states x_i = (q_i, v_i) and x_{i+1}, `dt` apart, the posterior mean of the constant-velocity GP prior is
 
@@ -59,3 +59,32 @@ def interpolate(trajs, n_sub, dt):
     out[..., 0:-1:k1, :] = a                      # support states are copies
     out[..., -1, :] = x[..., -1, :]
     return out
+
+
+def inserted_indices(T, n_sub):
+    """Fine indices of the INSERTED states (m = 1 .. n_sub of every interval), ascending: the states the collision part of
+    `sgpmp_dense_cost` covers.  The support states f = i (n_sub + 1) are the cost sweep's."""
+    f = np.arange(fine_length(T, n_sub), dtype=np.int64)
+    return f[f % (int(n_sub) + 1) != 0]
+
+
+def limit_penalty(fine, q_limits=None, v_limits=None, sigma_limit=None):
+    """The limit part of `sgpmp_dense_cost` on fine states [..., T_f, 2n] -> [...], in fp64:
+    1/sigma_limit^2 sum over states and dof of max(0, q_lo - q)^2 + max(0, q - q_hi)^2 + max(0, |q'| - v_max)^2.
+    q_limits = (lower [n], upper [n]), either may be None; v_limits [n].  A limit that is not given contributes nothing."""
+    x = np.asarray(fine, dtype=np.float64)
+    n = x.shape[-1] // 2
+    q, v = x[..., :n], x[..., n:]
+    out = np.zeros(x.shape[:-2], dtype=np.float64)
+    q_lo, q_hi = (None, None) if q_limits is None else q_limits
+    if q_lo is None and q_hi is None and v_limits is None:
+        return out
+    if sigma_limit is None or not float(sigma_limit) > 0.:
+        raise ValueError("limit_penalty: limits need sigma_limit > 0")
+    if q_lo is not None:
+        out += (np.maximum(np.asarray(q_lo, dtype=np.float64) - q, 0.) ** 2).sum(axis=(-2, -1))
+    if q_hi is not None:
+        out += (np.maximum(q - np.asarray(q_hi, dtype=np.float64), 0.) ** 2).sum(axis=(-2, -1))
+    if v_limits is not None:
+        out += (np.maximum(np.abs(v) - np.asarray(v_limits, dtype=np.float64), 0.) ** 2).sum(axis=(-2, -1))
+    return out / float(sigma_limit) ** 2

@@ -563,6 +563,19 @@ class Engine:
             L.check(self.lib.sgpmp_interpolate(self._ctx, L.ptr(trajs), B, n_sub, float(dt), L.ptr(out), L.stream_ptr()))
         return out
 
+    def _host_limits(self, q_limits, v_limits):
+        """(q_lo, q_hi, v_max) as host double[n] arrays or None, from q_limits = (lower, upper) (either may be None) and
+        v_limits [n]: what sgpmp_validate and sgpmp_dense_cost take."""
+        def host(v):
+            if v is None:
+                return None
+            vals = [float(x) for x in torch.as_tensor(v, dtype=torch.float64).flatten()]
+            if len(vals) != self.n:
+                raise ValueError(f"limits: expected {self.n} numbers, got {len(vals)}")
+            return (C.c_double * self.n)(*vals)
+        q_lo, q_hi = (None, None) if q_limits is None else (host(q_limits[0]), host(q_limits[1]))
+        return q_lo, q_hi, host(v_limits)
+
     def validate(self, trajs, n_sub, dt, spheres=None, grid_term=-1, q_limits=None, v_limits=None):
         """Check of ALL fine states of trajs [B,T,d] -> (values [B,4], where [B,4] int32): obstacle clearance, self-clearance,
         limit excess, grid occupancy and the first fine index attaining each (include/sgpmp.h: sgpmp_validate).
@@ -575,21 +588,47 @@ class Engine:
             self._chk(spheres, "obstacle_spheres")
             n_sph = spheres.shape[0]
 
-        def host(v):
-            if v is None:
-                return None
-            vals = [float(x) for x in torch.as_tensor(v, dtype=torch.float64).flatten()]
-            if len(vals) != self.n:
-                raise ValueError(f"limits: expected {self.n} numbers, got {len(vals)}")
-            return (C.c_double * self.n)(*vals)
-        q_lo, q_hi = (None, None) if q_limits is None else (host(q_limits[0]), host(q_limits[1]))
-        v_max = host(v_limits)
+        q_lo, q_hi, v_max = self._host_limits(q_limits, v_limits)
         values = torch.empty(B, 4, **self.tensor_args)
         where = torch.empty(B, 4, device=self.device, dtype=torch.int32)
         with torch.cuda.device(self.device):
             L.check(self.lib.sgpmp_validate(self._ctx, L.ptr(trajs), B, int(n_sub), float(dt), L.ptr(spheres), n_sph,
                                             int(grid_term), q_lo, q_hi, v_max, L.ptr(values), L.ptr(where), L.stream_ptr()))
         return values, where
+
+    def dense_cost(self, trajs, n_sub, dt, spheres=None, weight=1.0, q_limits=None, v_limits=None, sigma_limit=None,
+                   out=None, out64=None, accumulate=False):
+        """Continuous-time cost of trajs [B,T,d]: weight x the collision terms of the cost program on the `n_sub` GP-interpolated
+        states inserted per interval, plus 1/sigma_limit^2 x the squared joint / velocity limit excess over all fine states
+        (include/sgpmp.h: sgpmp_dense_cost; numpy twin of the limit part: dense.limit_penalty).  accumulate: add to what
+        `out` / `out64` hold -- sgpmp_cost_eval's outputs -- instead of writing.  -> out (ctx dtype), or out64 when only that is given."""
+        self._chk(trajs, "trajs")
+        B = trajs.numel() // (self.T * self.d)
+        if out is None and out64 is None:
+            if accumulate:
+                raise ValueError("dense_cost: accumulate needs the tensor to add to (out / out64)")
+            out = torch.empty(B, **self.tensor_args)
+        self._chk(out, "out")
+        if out64 is not None and (not out64.is_cuda or out64.dtype != torch.float64 or not out64.is_contiguous()):
+            raise ValueError("dense_cost: out64 must be a contiguous float64 tensor on the device")
+        for o in (out, out64):
+            if o is not None and o.numel() != B:
+                raise ValueError(f"dense_cost: outputs hold {o.numel()} numbers, the batch is {B}")
+        n_sph = 0
+        if spheres is not None:
+            spheres = spheres.reshape(-1, 4)
+            self._chk(spheres, "obstacle_spheres")
+            n_sph = spheres.shape[0]
+        q_lo, q_hi, v_max = self._host_limits(q_limits, v_limits)
+        with torch.cuda.device(self.device):
+            L.check(self.lib.sgpmp_dense_cost(self._ctx, L.ptr(trajs), B, int(n_sub), float(dt), L.ptr(spheres), n_sph,
+                                              float(weight), q_lo, q_hi, v_max, 0.0 if sigma_limit is None else float(sigma_limit),
+                                              1 if accumulate else 0, L.ptr(out), L.ptr(out64), L.stream_ptr()))
+        return out if out is not None else out64
+
+    def last_dense_kernel(self):
+        """Name of the kernel this thread's last dense_cost() launched ("" before the first)."""
+        return self.lib.sgpmp_last_dense_kernel().decode()
 
     # ------------------------------------------------------------------ GPMP (Gauss-Newton planner)
     def gpmp_linearize(self, means, spheres=None, diag_sum=None):

@@ -45,6 +45,12 @@ class GPMP(StochGPMP):
                          sigma_gp_init=sigma_gp_init, sigma_gp_sample=sigma_gp_sample, seed=seed,
                          tensor_args=tensor_args, **kwargs)
 
+    def set_dense_cost(self, setting=None, **kw):
+        """The continuous-time term enters StochGPMP's sampled cost only; the Gauss-Newton linear system has no such factor."""
+        if setting is not None or kw:
+            raise NotImplementedError("GPMP: dense_cost is an option of StochGPMP (no continuous-time factor in the linear system)")
+        self._dense = None
+
     def get_dist(self, start_K, gp_K, goal_K, state_init, particle_means=None, goal_states=None):
         """planner.py:479-501: a stand-alone MultiMPPrior of this problem (the same object StochGPMP.get_prior_dist builds)."""
         return self.get_prior_dist(start_K, gp_K, goal_K, state_init, particle_means=particle_means, goal_states=goal_states)

@@ -196,8 +196,11 @@ class StochGPMP:
         self.c_loop = bool(kwargs.get('c_loop', True))
         self.f64_fields_f32 = bool(kwargs.get('f64_fields_f32', False))
         self._mode_buf = None
+        self._dense = None
 
         self.reset(start_state, multi_goal_states, initial_particle_means=initial_particle_means)
+        # continuous-time collision / limit cost on the GP-interpolated states between the waypoints (no reference counterpart)
+        self.set_dense_cost(kwargs.get('dense_cost', None))
 
     # ------------------------------------------------------------------------------- factors
     def set_prior_factors(self):
@@ -485,6 +488,80 @@ class StochGPMP:
             allreduce_mode_sums(buf, self.process_group)
         return mode_moments(buf, self.traj_len, self.d_state_opt)
 
+    # ------------------------------------------------------------------------------- continuous-time cost
+    def set_dense_cost(self, setting=None, **kw):
+        """Make the states BETWEEN the support waypoints count in the cost that drives the optimisation: with
+        dict(n_sub=4, weight=1.0, q_limits=None, v_limits=None, sigma_limit=None) (or the same as keywords) every step adds
+        weight x the collision terms of the cost program on the n_sub GP-interpolated states per interval and
+        1/sigma_limit^2 x the squared joint (q_limits = (lower, upper)) / velocity (v_limits) limit excess over all fine states
+        to each sample's cost (include/sgpmp.h: sgpmp_dense_cost).  None switches it off: the planner is then bit for bit
+        the one without the option.  While it is on, step() runs sample -> costs -> update as separate launches and
+        optimize() loops over step()."""
+        if setting is None and not kw:
+            self._dense = None
+            return
+        cfg = dict(n_sub=4, weight=1.0, q_limits=None, v_limits=None, sigma_limit=None)
+        given = dict(setting or {}, **kw)
+        unknown = set(given) - set(cfg)
+        if unknown:
+            raise ValueError(f"dense_cost: unknown keys {sorted(unknown)}")
+        cfg.update(given)
+        if not self._native_cost:
+            raise ValueError("dense_cost needs a cost the library evaluates itself (a CostComposite compiled into the engine)")
+        cfg['n_sub'], cfg['weight'] = int(cfg['n_sub']), float(cfg['weight'])
+        if not 0 <= cfg['n_sub'] <= L.MAX_SUBSTEPS or not cfg['weight'] >= 0.:
+            raise ValueError(f"dense_cost: n_sub in [0, {L.MAX_SUBSTEPS}] and weight >= 0")
+        ql = cfg['q_limits']
+        limits = (ql is not None and (ql[0] is not None or ql[1] is not None)) or cfg['v_limits'] is not None
+        if limits and (cfg['sigma_limit'] is None or not float(cfg['sigma_limit']) > 0.):
+            raise ValueError("dense_cost: limits need sigma_limit > 0")
+        self._dense = cfg
+
+    def _dense_record(self):
+        """The setting as plain numbers (state_dict)."""
+        if self._dense is None:
+            return None
+        def plain(v):
+            return None if v is None else [float(x) for x in torch.as_tensor(v, dtype=torch.float64).flatten()]
+        c = self._dense
+        ql = c['q_limits']
+        return {'n_sub': c['n_sub'], 'weight': c['weight'],
+                'q_limits': None if ql is None else [plain(ql[0]), plain(ql[1])], 'v_limits': plain(c['v_limits']),
+                'sigma_limit': None if c['sigma_limit'] is None else float(c['sigma_limit'])}
+
+    def _add_dense_cost(self, trajs, spheres, out=None, out64=None):
+        c = self._dense
+        self._engine.dense_cost(trajs, c['n_sub'], self.dt, spheres=spheres, weight=c['weight'], q_limits=c['q_limits'],
+                                v_limits=c['v_limits'], sigma_limit=c['sigma_limit'], out=out, out64=out64, accumulate=True)
+
+    def _step_dense_cost(self, **observation):
+        """step() with the continuous-time term: sgpmp_sample, sgpmp_cost_eval with the importance-sampling weights,
+        sgpmp_dense_cost adding into the same costs, sgpmp_update."""
+        eng, slot = self._engine, self._stats_slot
+        cv = self.cost.version()
+        if cv != self._cost_version:
+            self.cost.compile_into(eng)
+            self._cost_version = cv
+        eps = self._draw_eps()
+        stats = self._stats[slot]
+        stats.zero_()
+        if self.num_particles_local > 0:
+            eng.sample(L.PRIOR_SAMPLE, self.seed, self._draw, self.particle_means, self.num_samples,
+                       out=self.state_samples, eps=eps, eps_mode_offset=self.p0 if eps is not None else 0,
+                       mode_offset=self.p0)
+            self._get_costs(**observation)
+            self._costs64_fresh = False
+            eng.update(self._costs64, self.state_samples, self.particle_means, self.temperature, self.step_size,
+                       weights=self._weights_buf, grad=self._grad, means_prev=self._means_prev, stats=stats)
+        if self._comm_attached:
+            eng.allreduce_stats(stats)                   # (a collective: an empty shard joins it too)
+        self._pm_obj, self._pm_version = None, -1        # (no importance-sampling weights prepared for the next step)
+        self._mode_fresh = False
+        self._draw += 1
+        self._reduce_stats(slot)
+        self._stats_slot ^= 1
+        return self._costs, self._grad
+
     # ------------------------------------------------------------------------------- the loop
     def step(self, _means_prev_out=None, _samples_unread=False, **observation):
         """One body of the loop at planner.py:289-299 on this rank's particle shard.  (_means_prev_out: where this step leaves
@@ -496,6 +573,8 @@ class StochGPMP:
         self._means_prev = prev_out
         if not self._native_cost:
             return self._step_foreign_cost(**observation)
+        if self._dense is not None:
+            return self._step_dense_cost(**observation)
         slot = self._stats_slot
         cv = self.cost.version()
         if cv != self._cost_version:                     # a field / cost was edited (e.g. update_target)
@@ -574,6 +653,8 @@ class StochGPMP:
             eng.cost_eval(self.state_samples, batch_offset=self.p0 * S,
                           spheres=self._spheres(observation), is_weights=isw, rows_per_particle=S,
                           out=self._costs, out64=self._costs64)
+            if self._dense is not None:
+                self._add_dense_cost(self.state_samples, self._spheres(observation), out=self._costs, out64=self._costs64)
             self._costs64_fresh = True       # fp64 twin of the costs just returned
             return self._costs
         user = self.cost.eval(self.state_samples, **observation).reshape(Pl, S)
@@ -621,9 +702,9 @@ class StochGPMP:
             and self._collective == 'torch' and torch.distributed.is_initialized()   # (reads the statistics per step)
         piped = (opt_iters >= 2 and not debug and self._native_cost and self.noise == 'philox'
                  and self.num_particles_local > 0 and self.pipeline_steps and not torch_reduce
-                 and not self.mode_stats_every_step)
+                 and not self.mode_stats_every_step and self._dense is None)
         if (not debug and self._native_cost and self.noise == 'philox' and self.num_particles_local > 0
-                and not torch_reduce and opt_iters >= 1 and self.c_loop):
+                and not torch_reduce and opt_iters >= 1 and self.c_loop and self._dense is None):
             return self._optimize_one_call(opt_iters, piped, observation)
         if piped:
             self._spheres(observation)                   # (a first use copies on THIS stream: before the chains fork)
@@ -758,6 +839,8 @@ class StochGPMP:
             for g in range(G):                               # (row offset g nppg S: the goal prior looks goal g up)
                 self._engine.cost_eval(means[g * nppg:(g + 1) * nppg], batch_offset=g * nppg * S, spheres=sph,
                                        out=costs[g * nppg:(g + 1) * nppg])
+            if self._dense is not None:                      # the score the optimisation minimised
+                self._add_dense_cost(self._dense_input(means), sph, out=costs)
         else:
             costs = self.cost.eval(means, **observation).reshape(-1).to(**self.tensor_args)
         masked = torch.where(val.valid, costs, torch.full_like(costs, float('inf'))).reshape(G, nppg)
@@ -805,6 +888,7 @@ class StochGPMP:
             'stats': self._stats.detach().clone(),
             'temperature': self.temperature, 'step_size': self.step_size, 'noise': self.noise,
             'cost_version': self.cost.version() if self._native_cost else None,
+            'dense_cost': self._dense_record(),
             # rows that carried weight in each particle's last update: the next step's launch / update decide on them per
             # particle (partials or rows: equal to 1e-6 only), so a bit-for-bit continuation needs them
             'row_counts': torch.from_numpy(self._engine.row_counts().astype('int64')),
@@ -841,6 +925,10 @@ class StochGPMP:
             import warnings
             warnings.warn("load_state_dict: the state was taken under another version of the cost program "
                           f"({sd['cost_version']} != {self.cost.version()}); the run continues on the current one")
+        if sd.get('dense_cost') != self._dense_record():
+            import warnings
+            warnings.warn("load_state_dict: the state was taken under another dense_cost setting "
+                          f"({sd.get('dense_cost')} != {self._dense_record()}); the run continues on the current one")
         rc = sd.get('row_counts')
         self._engine.set_row_counts(None if rc is None else rc[self.p0 - q0:self.p1 - q0].numpy())
         if self.noise == 'torch' and 'torch_rng_state' in sd:
