@@ -98,7 +98,6 @@ struct sgpmp_ctx {
     unsigned* d_nnz = nullptr;       // [P], allocated (zero) by the first fp32 step
     long long dense_armed_steps = 0, store_free_steps = 0;
     long long multi_iteration_launches = 0;
-    int tail_iters_next = 0;         // sgpmp_optimize -> its next sgpmp_step: iterations the step's launch runs itself (fused_planar_seg.inc: PERSIST)
     int last_step_launches = 0;      // kernels the last sgpmp_step enqueued for its particle range (1: everything in one launch)
     hipStream_t k1_side = nullptr;   // sgpmp_set_priors: the second factorisation's stream
     hipEvent_t k1_fork = nullptr;
@@ -135,9 +134,9 @@ static void toggles_from_env(SgpmpToggles& tg) {
 
 #ifdef SGPMP_HOST_TIMING      // diagnostic build (tools/host_step_cost.py): host nanoseconds of sgpmp_step's segments, printed by sgpmp_destroy
 #include <ctime>
-static double g_ht[8]; static long long g_htn;
+static double g_ht[8], ht_t; static long long g_htn;
 static inline double ht_now() { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return 1e9 * (double)t.tv_sec + (double)t.tv_nsec; }
-#define HT_START() double ht_t = ht_now()
+#define HT_START() ht_t = ht_now()
 #define HT(i) do { const double n_ = ht_now(); g_ht[i] += n_ - ht_t; ht_t = n_; } while (0)
 #else
 #define HT_START() do {} while (0)
@@ -364,7 +363,7 @@ extern "C" int sgpmp_allgather_means(sgpmp_ctx* c, const void* local_means, void
 extern "C" void sgpmp_destroy(sgpmp_ctx* c) {
 #ifdef SGPMP_HOST_TIMING
     if (g_htn) {
-        std::fprintf(stderr, "[host timing] %lld steps: checks+split %.2f us, eligibility %.2f, fused launch %.2f, update launch %.2f\n", g_htn,
+        std::fprintf(stderr, "[host timing] %lld steps: checks %.2f us, plan+split %.2f, fused launch %.2f, update launch %.2f\n", g_htn,
                      1e-3 * g_ht[0] / g_htn, 1e-3 * g_ht[1] / g_htn, 1e-3 * g_ht[2] / g_htn, 1e-3 * g_ht[3] / g_htn);
         g_htn = 0; for (double& v : g_ht) v = 0.;
     }
@@ -1025,12 +1024,8 @@ extern "C" int sgpmp_update(sgpmp_ctx* c, const void* costs, int costs_dtype, co
     return SGPMP_OK;
 }
 
-// The step's end-effector goal term goes INTO update_kernel (update_common.h: EeFold) when it is the only one and the kernel's
-// scratch has room: one launch less per iteration (the term is a few hundred flops per trajectory; as a launch of its own it
-// cost 6 us of the reference's Panda example's 24).  -> the term, or null: ee_goal_kernel in front of update_kernel as before.
+// the end-effector goal term update_kernel evaluates itself (StepPlan::ee == STEP_EE_FOLD: the program has exactly one)
 static const CostTerm* ee_term_to_fold(const sgpmp_ctx* c) {
-    if (c->tg.no_ee_fold || c->h_prog.n_ee != 1) return nullptr;
-    if (!update_ee_fold_fits(c->dims.dtype, c->dims.n_dof, c->dims.traj_len, c->dims.num_samples)) return nullptr;
     for (int i = 0; i < c->h_prog.n_terms; ++i)
         if (c->h_prog.terms[i].kind == SGPMP_COST_EE_GOAL) return &c->h_prog.terms[i];
     return nullptr;
@@ -1049,8 +1044,6 @@ static int dense_buffers(sgpmp_ctx* c, FusedDenseHost* d, double temperature, bo
     // rows of a store-free step: kept for particles that wanted more rows than update_kernel regenerates in one round --
     // and for every particle that gets partials (they re-read the rows): never above the partials' threshold
     d->store_threshold = d->threshold < 4u ? d->threshold : 4u;
-    d->particles_total = D.num_particles;
-    d->particles_global = D.num_particles_global > 0 ? D.num_particles_global : D.num_particles;
     if (D.dtype != SGPMP_F32 || D.num_particles < 1) return SGPMP_OK;
     if (!c->d_nnz) {
         const size_t P = (size_t)D.num_particles;
@@ -1169,23 +1162,126 @@ extern "C" int sgpmp_pipeline_end(sgpmp_ctx* c, void* stream) {
     return pipe_join(c, (hipStream_t)stream);
 }
 
-// One step as two half-range launch sequences on the chains' own streams (see StepPipe).  The caller has checked
-// that both halves qualify for the fused launch.
-static int step_split(sgpmp_ctx* c, uint64_t seed, uint64_t draw, char* means, char* samples, char* costs,
-                      char* weights, char* grad, char* means_prev, const void* spheres, int n_spheres,
-                      double temperature, double step_size, double* stats, int flags, hipStream_t st) {
+// ---- one step --------------------------------------------------------------------------------------------------
+struct StepArgs {                 // what sgpmp_step was given
+    uint64_t seed, draw;
+    const void* eps; int eps_modes, eps_mode_offset;
+    char *means, *samples, *costs, *weights, *grad, *means_prev;
+    const void* spheres; int n_spheres;
+    double temperature, step_size;
+};
+
+// particles [first, first + P) of this context's range
+static StepShape step_shape(const sgpmp_ctx* c, int P, int first, int n_spheres) {
     const sgpmp_dims& D = c->dims;
-    const int P = D.num_particles, S = D.num_samples, P0 = pipe_first_half(c);
+    return {D.dtype, D.n_dof, D.traj_len, D.num_samples, n_spheres, P, D.particle_offset + first, D.num_particles,
+            D.num_particles_global > 0 ? D.num_particles_global : D.num_particles};
+}
+static StepPlan plan_range(const sgpmp_ctx* c, int P, int first, int n_spheres, const StepWants& wants) {
+    return plan_step(step_shape(c, P, first, n_spheres), wants, c->prior[SGPMP_PRIOR_SAMPLE], c->h_prog, c->h_chain, c->tg);
+}
+
+// Does the step run as two half-range chains (StepPipe)?  `bracket`: inside sgpmp_pipeline_begin .. _end.  Both halves must be
+// big enough to fill the chip on their own (256 workgroups of 4 items of 8 rows) and fused; half[] gets their plans.
+static bool plan_two_chains(const sgpmp_ctx* c, bool bracket, const StepWants& wants, const StepPlan& whole, StepPlan half[2]) {
+    const sgpmp_dims& D = c->dims;
+    // (fp32 steps only: an fp64 step's launch is 0.5 - 0.8 ms of vector arithmetic at two waves per SIMD with a per-workgroup
+    // prologue -- two half-size launches side by side measured 6 % SLOWER than one, and the update is 2 % of the step)
+    if (!bracket || wants.eps || c->profiling || c->tg.no_step_pipeline || c->ms_buf || D.dtype != SGPMP_F32) return false;
+    const int P = D.num_particles, P0 = pipe_first_half(c);
+    // (fused_planar_seg_kernel: a workgroup is 16 waves, one per particle and 64 samples -- a half must still
+    // bring a workgroup for every CU, or two half-empty launches take turns: 40.3 k against 44.4 k it/s at config 2)
+    const bool seg = (whole.family == STEP_PLANAR_SEG || whole.family == STEP_PLANAR_TILE) && whole.L != 0;
+    if ((long long)(P0 < P - P0 ? P0 : P - P0) * D.num_samples < (seg ? 256 * 64 : 256 * 4 * 8)) return false;
+    half[0] = plan_range(c, P0, 0, whole.shape.n_spheres, wants);
+    half[1] = plan_range(c, P - P0, P0, whole.shape.n_spheres, wants);
+    return half[0].family != STEP_NONE && half[1].family != STEP_NONE;
+}
+
+// The launch sequence of ONE particle range -- the plan's P particles from `first` on -- on `st`, statistics into `slot`:
+// importance-sampling weights unless prepared, the fused launch or sampler + sweep, the end-effector launch if the plan says
+// so, the update unless the launch carried it.  h: which of the context's in-launch update counters the range uses.
+// -> the kernels it enqueued, or an error code (< 0)
+static int run_range(sgpmp_ctx* c, const StepPlan& plan, const StepArgs& a, size_t first, int h, bool prepared,
+                     const FusedDenseHost& dense, hipStream_t st, double* slot, hipEvent_t k4_done, StepEvents* se,
+                     void* means_copy, bool* isw_written) {
+    const sgpmp_dims& D = c->dims;
+    const int P = plan.shape.P, S = D.num_samples;
     const PriorDev& pr = c->prior[SGPMP_PRIOR_SAMPLE];
     const size_t w = c->esz, M = (size_t)c->M, W = (size_t)(D.traj_len + 1) * c->d;
+    char* mu = a.means + first * M * w;
+    char* X = a.samples + first * S * M * w;
+    char* isw = (char*)c->d_isw + first * W * w;
+    char* cs = a.costs ? a.costs + first * S * w : nullptr;
+    double* c64 = c->d_costs64 + first * S;
+    char* wh = a.weights ? a.weights + first * S * w : nullptr;
+    char* gh = a.grad ? a.grad + first * M * w : nullptr;
+    char* mph = a.means_prev ? a.means_prev + first * M * w : nullptr;
+    int launches = 0;
+    // K5 is skipped when the previous step's update kernel already prepared the weights for exactly these means; the fused
+    // launch (or the sampler) then zeroes the statistics itself
+    if (!prepared) {
+        HIPCHK(launch_is_weights(D.dtype, D.n_dof, D.traj_len, pr, mu, P, a.temperature, isw, slot, st));
+        launches += 1;
+    }
+    if (se) { HIPCHK(hipEventRecord(se->ev[1], st)); se->has[0] = !prepared; }
+    StepIo io = {&pr, &c->h_prog, &c->h_chain, a.seed, a.draw, mu, X, a.spheres, isw, slot, cs, c64, st, dense};
+    if (io.dense.part) io.dense.part += first * (size_t)((S + 7) / 8) * (size_t)(c->M + 4);
+    if (io.dense.nnz) io.dense.nnz += first;
+    const CostTerm* eet = nullptr;                               // the end-effector goal term update_kernel evaluates itself
+    if (plan.family != STEP_NONE) {
+        // One fused launch (sampler + cost sweep; in-kernel noise)
+        if (se) { HIPCHK(hipEventRecord(se->ev[2], st)); se->has[1] = false; }   // (fused: the whole launch is booked on the sweep)
+        io.dense.tail_done = c->d_done + h; io.dense.tail_acc = c->d_tail_acc + (size_t)h * SGPMP_STAT_SHARDS * 4; io.dense.stats_out = slot;
+        io.dense.weights = wh; io.dense.grad = gh; io.dense.means_prev = mph; io.dense.step_size = a.step_size;
+        HIPCHK(launch_fused_step(plan, io));
+        c->last_cost_kernel = plan.kernel;
+        launches += 1;
+        if (plan.ee == STEP_EE_FOLD) eet = ee_term_to_fold(c);
+        for (int i = 0; plan.ee == STEP_EE_LAUNCH && i < c->h_prog.n_terms; ++i)
+            if (c->h_prog.terms[i].kind == SGPMP_COST_EE_GOAL) {
+                HIPCHK(launch_ee_goal(D.dtype, D.n_dof, D.traj_len, c->h_prog.terms[i], c->d_chain, X, (long long)P * S, cs, c64, st));
+                launches += 1;
+            }
+    } else {
+        // the sampler and the sweep one after the other (launch_cost runs the end-effector terms behind the sweep)
+        HIPCHK(launch_sample(D.dtype, D.n_dof, D.traj_len, pr, a.seed, a.draw, mu, P, plan.shape.offset, S, a.eps,
+                             a.eps_modes, a.eps_mode_offset, X, st, c->tg, prepared ? slot : nullptr));
+        if (se) HIPCHK(hipEventRecord(se->ev[2], st));
+        HIPCHK(launch_cost(D.dtype, D.n_dof, D.traj_len, c->h_prog, c->d_chain, c->h_chain, X, (long long)P * S,
+                           (long long)plan.shape.offset * S, a.spheres, a.n_spheres, isw, S, pr.dt, cs, c64, st, c->tg,
+                           &c->last_cost_kernel));
+        launches += 2;
+    }
+    HT(2);                                                       // the fused launch (or sampler + sweep)
+    if (se) HIPCHK(hipEventRecord(se->ev[3], st));
+    // (the update also prepares the NEXT step's importance-sampling weights -- unless, as a kernel of its own, the new
+    // means do not fit its LDS beside the weights: launch_update decides)
+    *isw_written = plan.update_in_launch;
+    if (plan.update_in_launch) {                                 // (fused_planar_seg.inc: seg_update)
+        if (k4_done) HIPCHK(hipEventRecord(k4_done, st));
+    } else {
+        const RegenHost regen = plan_regen(plan, pr, a.seed, a.draw, dense.store_threshold);
+        const EeFoldHost eeh = {eet, c->d_chain, cs};
+        HIPCHK(launch_update(D.dtype, D.n_dof, D.traj_len, P, S, c64, SGPMP_F64, X, mu, a.temperature, a.step_size, wh, gh, mph,
+                             slot, st, c->tg.comm_packet_event ? k4_done : nullptr, &pr, isw, isw_written, means_copy,
+                             plan.partials ? io.dense.part : nullptr, io.dense.nnz, dense.threshold,
+                             regen.recipe != 0 ? &regen : nullptr, eet ? &eeh : nullptr));
+        if (!c->tg.comm_packet_event && k4_done) HIPCHK(hipEventRecord(k4_done, st));
+        launches += 1;
+    }
+    HT(3);                                                       // the update launch
+    return launches;
+}
+
+// One step as two half-range launch sequences on the chains' own streams (see StepPipe).
+static int step_two_chains(sgpmp_ctx* c, const StepArgs& a, const StepPlan half[2], bool prepared, const FusedDenseHost& dense,
+                           double* stats, hipStream_t st) {
     int rc;
     // (Tried: chain 0's first launch as two quarter-range launches with chain 1 starting behind the first, so that the
     // chains are out of phase from the first iteration on -- no gain; a call's fixed cost of ~0.1 ms is the fill
     // and drain of the two-stage schedule itself, about half a sampler + sweep launch.)
     if ((rc = pipe_fork(c, st)) != SGPMP_OK) return rc;
-    const bool prepared = (flags & SGPMP_STEP_MEANS_KEPT) && c->isw_ready && c->isw_means == (const void*)means &&
-                          c->isw_temperature == temperature;
-    c->isw_ready = false;
     // multi-GPU: each chain accumulates into its block of a ring slot; the all-reduce (communicator's stream) waits
     // for both update kernels, adds the blocks and writes the sums over all ranks into the caller's `stats`
     const bool reduce = c->comm && stats;
@@ -1194,59 +1290,19 @@ static int step_split(sgpmp_ctx* c, uint64_t seed, uint64_t draw, char* means, c
     bool isw_next[2] = {false, false};
     if (reduce)
         COMMCHK(comm_step_begin2(c->comm, c->pipe.side[0], c->pipe.side[1], &slots[0], &slots[1], &k4_done[0], &k4_done[1]));
-    FusedDenseHost dense;                                        // (once per step: both halves share the buffers)
-    if ((rc = dense_buffers(c, &dense, temperature, c->h_prog.needs_fk != 0)) != SGPMP_OK) return rc;
-    dense.nostore = (flags & SGPMP_STEP_NO_SAMPLES) ? 1 : 0;
-    if (dense.part) c->dense_armed_steps += 1;
     for (int h = 0; h < 2; ++h) {
-        const size_t off = h ? (size_t)P0 : 0;
-        const int Ph = h ? P - P0 : P0;
-        hipStream_t sh = c->pipe.side[h];
-        double* slot = slots[h];
-        char* mu = means + off * M * w;
-        char* X = samples + off * S * M * w;
-        char* isw = (char*)c->d_isw + off * W * w;
-        char* cs = costs ? costs + off * S * w : nullptr;
-        double* c64 = c->d_costs64 + off * S;
-        if (!prepared) HIPCHK(launch_is_weights(D.dtype, D.n_dof, D.traj_len, pr, mu, Ph, temperature, isw, slot, sh));
-        bool launched = false;
-        char* wh = weights ? weights + off * S * w : nullptr;
-        char* gh = grad ? grad + off * M * w : nullptr;
-        char* mph = means_prev ? means_prev + off * M * w : nullptr;
-        FusedDenseHost dh = dense;
-        if (dh.part) dh.part += off * (size_t)((S + 7) / 8) * (size_t)(c->M + 4);
-        if (dh.nnz) dh.nnz += off;
-        dh.tail_done = c->d_done + h; dh.tail_acc = c->d_tail_acc + (size_t)h * SGPMP_STAT_SHARDS * 4; dh.stats_out = slot;
-        dh.weights = wh; dh.grad = gh; dh.means_prev = mph; dh.step_size = step_size;
-        bool armed = false, tail_ran = false;
-        RegenHost rgh;
-        HIPCHK(launch_fused_step(D.dtype, D.n_dof, D.traj_len, pr, c->h_prog, c->h_chain, seed, draw, mu, Ph,
-                                 D.particle_offset + (int)off, S, X, spheres, n_spheres, isw, slot, cs, c64, sh, c->tg,
-                                 &c->last_cost_kernel, &launched, &dh, &armed, &rgh, &tail_ran));
-        if (!launched) return fail(SGPMP_ESTATE, "sgpmp_step: a half of a pipelined step did not qualify for the fused launch");
-        c->last_step_launches = 1;
-        if (tail_ran) {                                          // the launch updated its particles itself (fused_planar_seg.inc: seg_update)
-            isw_next[h] = true;
-            if (h == 0) c->store_free_steps += 1;
-            if (k4_done[h]) HIPCHK(hipEventRecord(k4_done[h], sh));
-            continue;
-        }
-        const CostTerm* eet = ee_term_to_fold(c);
-        const EeFoldHost eeh = {eet, c->d_chain, cs};
-        for (int i = 0; !eet && i < c->h_prog.n_terms; ++i)
-            if (c->h_prog.terms[i].kind == SGPMP_COST_EE_GOAL) {
-                HIPCHK(launch_ee_goal(D.dtype, D.n_dof, D.traj_len, c->h_prog.terms[i], c->d_chain, X,
-                                      (long long)Ph * S, cs, c64, sh));
-                c->last_step_launches += 1;
-            }
-        HIPCHK(launch_update(D.dtype, D.n_dof, D.traj_len, Ph, S, c64, SGPMP_F64, X, mu, temperature, step_size, wh, gh, mph,
-                             slot, sh, c->tg.comm_packet_event ? k4_done[h] : nullptr, &pr, isw, &isw_next[h], nullptr,
-                             armed ? dh.part : nullptr, dh.nnz, dh.threshold, &rgh, eet ? &eeh : nullptr));
-        if (h == 0 && rgh.recipe != 0) c->store_free_steps += 1;
-        if (!c->tg.comm_packet_event && k4_done[h]) HIPCHK(hipEventRecord(k4_done[h], sh));
-        c->last_step_launches += 1;
+        const int launches = run_range(c, half[h], a, h ? (size_t)half[0].shape.P : 0, h, prepared, dense, c->pipe.side[h], slots[h],
+                                       k4_done[h], nullptr, nullptr, &isw_next[h]);
+        if (launches < 0) return launches;
+        // The counters of a two-chain step differ from an ordinary step's in two ways, both kept as sgpmp.h words them:
+        // sgpmp_last_step_launches is "per chain" and has never counted a chain's importance-sampling weights launch (only the
+        // first step of a bracket has one); armed_steps counts "steps launched WITH the partials buffer", which a step with a
+        // separate end-effector launch has but does not use.
+        c->last_step_launches = launches - (prepared ? 0 : 1);
     }
-    c->isw_ready = isw_next[0] && isw_next[1]; c->isw_means = means; c->isw_temperature = temperature;
+    if (dense.part) c->dense_armed_steps += 1;
+    if (half[0].update_in_launch || half[0].regen_recipe != 0) c->store_free_steps += 1;
+    c->isw_ready = isw_next[0] && isw_next[1];
     if (reduce) COMMCHK(comm_step_end(c->comm, stats, true));
     c->pipe.last_stats = reduce ? nullptr : stats;
     c->pipe.split_steps += 1;
@@ -1256,10 +1312,12 @@ static int step_split(sgpmp_ctx* c, uint64_t seed, uint64_t draw, char* means, c
 extern "C" long long sgpmp_pipeline_split_steps(sgpmp_ctx* c) { return c ? c->pipe.split_steps : 0; }
 extern "C" int sgpmp_last_step_launches(sgpmp_ctx* c) { return c ? c->last_step_launches : 0; }
 
-extern "C" int sgpmp_step(sgpmp_ctx* c, uint64_t seed, uint64_t draw, const void* eps, int eps_modes,
-                          int eps_mode_offset, void* means, void* samples, void* costs, void* weights,
-                          void* grad, void* means_prev, const void* spheres, int n_spheres, double temperature,
-                          double step_size, double* stats, int flags, void* stream) {
+// sgpmp_step, with the number of iterations its ONE launch is to run (sgpmp_optimize: fused_planar_seg.inc, PERSIST).  Never
+// runs fewer than asked: SGPMP_ESTATE when the step would split into two chains or its plan cannot carry them.
+static int step_iters(sgpmp_ctx* c, int iters, uint64_t seed, uint64_t draw, const void* eps, int eps_modes,
+                      int eps_mode_offset, void* means, void* samples, void* costs, void* weights,
+                      void* grad, void* means_prev, const void* spheres, int n_spheres, double temperature,
+                      double step_size, double* stats, int flags, void* stream) {
     if (!c) return fail(SGPMP_EINVAL, "sgpmp_step: null context");
     HT_START();
     if (c->dims.num_particles == 0) {
@@ -1302,33 +1360,31 @@ extern "C" int sgpmp_step(sgpmp_ctx* c, uint64_t seed, uint64_t draw, const void
     int rc;
     if ((rc = finalize_program(c)) != SGPMP_OK) return rc;
     if ((rc = check_spheres(c, spheres, n_spheres)) != SGPMP_OK) return rc;
-    const sgpmp_dims& D = c->dims;
-    const int P = D.num_particles, S = D.num_samples;
+    const int P = c->dims.num_particles;
     if (eps && (eps_modes < 1 || eps_mode_offset < 0 || eps_mode_offset + P > eps_modes))
         return fail(SGPMP_EINVAL, "sgpmp_step: eps particle window out of range");
     hipStream_t st = (hipStream_t)stream;
-    const PriorDev& pr = c->prior[SGPMP_PRIOR_SAMPLE];
-    if (c->pipe.active) {
-        // both halves big enough to fill the chip on their own (256 workgroups of 4 items of 8 rows) and fused
-        const int P0 = pipe_first_half(c);
-        // (fused_planar_seg_kernel: a workgroup is 16 waves, one per particle and 64 samples -- a half must still
-        // bring a workgroup for every CU, or two half-empty launches take turns: 40.3 k against 44.4 k it/s at config 2)
-        const bool seg = planar_seg_step(D.dtype, D.n_dof, D.traj_len, pr, c->h_prog, c->h_chain, P, D.particle_offset, S,
-                                         n_spheres, c->tg);
-        // (fp32 steps only: an fp64 step's launch is 0.5 - 0.8 ms of vector arithmetic at two waves per SIMD with a per-workgroup
-        // prologue -- two half-size launches side by side measured 6 % SLOWER than one, and the update is 2 % of the step)
-        const bool split = !eps && !c->profiling && !c->tg.no_step_pipeline && !c->ms_buf && D.dtype == SGPMP_F32 &&
-                           (long long)(P0 < P - P0 ? P0 : P - P0) * S >= (seg ? 256 * 64 : 256 * 4 * 8) &&
-                           fused_step_eligible(D.dtype, D.n_dof, D.traj_len, pr, c->h_prog, c->h_chain, P0, D.particle_offset,
-                                               S, n_spheres, c->tg) &&
-                           fused_step_eligible(D.dtype, D.n_dof, D.traj_len, pr, c->h_prog, c->h_chain, P - P0,
-                                               D.particle_offset + P0, S, n_spheres, c->tg);
-        if (split)
-            return step_split(c, seed, draw, (char*)means, (char*)samples, (char*)costs, (char*)weights, (char*)grad,
-                              (char*)means_prev, spheres, n_spheres, temperature, step_size, stats, flags, st);
-        if ((rc = pipe_join(c, st)) != SGPMP_OK) return rc;      // an ordinary step: after the chains
-    }
-    HT(0);                                                       // checks + the pipeline's split decision
+    const StepArgs a = {seed, draw, eps, eps_modes, eps_mode_offset, (char*)means, (char*)samples, (char*)costs, (char*)weights,
+                        (char*)grad, (char*)means_prev, spheres, n_spheres, temperature, step_size};
+    HT(0);                                                       // checks
+    // (the per-step mean statistics want update_kernel's snapshot of the new means; they and the profiler read nothing of the
+    // samples: they do not stand in the way of a store-free step)
+    const StepWants wants = {eps != nullptr, (flags & SGPMP_STEP_NO_SAMPLES) != 0, !c->ms_buf, iters};
+    const StepPlan plan = plan_range(c, P, 0, n_spheres, wants);
+    StepPlan half[2];
+    const bool split = plan_two_chains(c, c->pipe.active, wants, plan, half);
+    if (iters > 1 && (split || plan.iters != iters))
+        return fail(SGPMP_ESTATE, "sgpmp_step: the step's launch cannot run the iterations asked of it (internal)");
+    HT(1);                                                       // the plan and the two-chain decision
+    const bool prepared = (flags & SGPMP_STEP_MEANS_KEPT) && c->isw_ready && c->isw_means == means && c->isw_temperature == temperature;
+    c->isw_ready = false; c->isw_means = means; c->isw_temperature = temperature;
+    // (two-launch steps record their row counts too: sgpmp.h's contract is "the counts of the last in-step update", and a
+    // later fused step or a checkpoint must not see those of an older one -- advisor finding, round 5)
+    FusedDenseHost dense;                                        // what the launch and the update share per particle (row counts, partials)
+    const bool fused = split || plan.family != STEP_NONE;
+    if ((rc = dense_buffers(c, &dense, temperature, fused && c->h_prog.needs_fk != 0)) != SGPMP_OK) return rc;
+    if (split) return step_two_chains(c, a, half, prepared, dense, stats, st);
+    if (c->pipe.active && (rc = pipe_join(c, st)) != SGPMP_OK) return rc;      // an ordinary step: after the chains
     StepEvents* se = nullptr;
     if (c->profiling) {
         c->events.emplace_back();
@@ -1342,104 +1398,40 @@ extern "C" int sgpmp_step(sgpmp_ctx* c, uint64_t seed, uint64_t draw, const void
     double* acc_stats = stats;
     hipEvent_t k4_done = nullptr;
     if (c->comm && stats) COMMCHK(comm_step_begin(c->comm, st, &acc_stats, &k4_done));
-    // One fused launch (importance-sampling weights + sampler + cost sweep) when the step qualifies
-    // (in-kernel noise, fp32 Panda-type program); else K5, the sampler and the sweep one after the other
-    bool fused = !eps && samples &&
-                 fused_step_eligible(D.dtype, D.n_dof, D.traj_len, pr, c->h_prog, c->h_chain, P, D.particle_offset, S,
-                                     n_spheres, c->tg);
-    // K5 is skipped when the previous step's update kernel already prepared the weights for exactly these
-    // means (the caller vouches with SGPMP_STEP_MEANS_KEPT that nothing else wrote them since); the fused
-    // launch then zeroes the statistics itself
-    HT(1);                                                       // eligibility
-    const bool prepared = (flags & SGPMP_STEP_MEANS_KEPT) && c->isw_ready && c->isw_means == means &&
-                          c->isw_temperature == temperature;
-    c->isw_ready = false;
-    if (!prepared)
-        HIPCHK(launch_is_weights(D.dtype, D.n_dof, D.traj_len, pr, means, P, temperature, c->d_isw, acc_stats, st));
-    if (se) { HIPCHK(hipEventRecord(se->ev[1], st)); se->has[0] = !prepared; }
-    c->last_step_launches = prepared ? 0 : 1;
-    FusedDenseHost dense;                                        // what the launch and the update share per particle (row counts, partials)
-    std::memset(&dense, 0, sizeof(dense));
-    bool partials = false, tail_ran = false;                     // tail_ran: the launch also updated its particles (fused_planar_seg.inc: seg_update)
-    RegenHost regen;                                             // store-free step: how the update regenerates rows
-    std::memset(&regen, 0, sizeof(regen));
-    const CostTerm* eet = nullptr;                               // the end-effector goal term update_kernel evaluates itself (fused steps)
-    if (fused) {
-        if (se) { HIPCHK(hipEventRecord(se->ev[2], st)); se->has[1] = false; }   // (fused: the whole launch is booked on the sweep)
-        if ((rc = dense_buffers(c, &dense, temperature, c->h_prog.needs_fk != 0)) != SGPMP_OK) return rc;
-        // (per-goal mean statistics and the profiler read nothing of the samples either: they do not stand in the way)
-        dense.nostore = (flags & SGPMP_STEP_NO_SAMPLES) ? 1 : 0;
-        if (!c->ms_buf) {                                        // (the per-step mean statistics want update_kernel's snapshot of the new means)
-            dense.tail_done = c->d_done; dense.tail_acc = c->d_tail_acc; dense.stats_out = acc_stats;
-            dense.weights = weights; dense.grad = grad; dense.means_prev = means_prev; dense.step_size = step_size;
-            dense.tail_iters = c->tail_iters_next;
-        }
-        HIPCHK(launch_fused_step(D.dtype, D.n_dof, D.traj_len, pr, c->h_prog, c->h_chain, seed, draw, means, P,
-                                 D.particle_offset, S, samples, spheres, n_spheres, c->d_isw, acc_stats, costs,
-                                 c->d_costs64, st, c->tg, &c->last_cost_kernel, &fused, &dense, &partials, &regen, &tail_ran));
-        if (fused) { c->last_step_launches += 1; if (partials) c->dense_armed_steps += 1; if (regen.recipe != 0 || tail_ran) c->store_free_steps += 1; }
-        if (dense.tail_iters > 1) {                              // (sgpmp_optimize checked that this step's launch carries its update)
-            if (!tail_ran) return fail(SGPMP_ESTATE, "sgpmp_step: the launch of several iterations did not run (internal)");
-            c->store_free_steps += dense.tail_iters - 1;
-            c->multi_iteration_launches += 1;
-        }
-        eet = fused ? ee_term_to_fold(c) : nullptr;
-        for (int i = 0; fused && !eet && i < c->h_prog.n_terms; ++i)
-            if (c->h_prog.terms[i].kind == SGPMP_COST_EE_GOAL) {
-                HIPCHK(launch_ee_goal(D.dtype, D.n_dof, D.traj_len, c->h_prog.terms[i], c->d_chain, samples,
-                                      (long long)P * S, costs, c->d_costs64, st));
-                c->last_step_launches += 1;
-            }
+    // per-goal mean statistics (sgpmp_set_step_mode_stats): the update kernel also leaves a snapshot of the new
+    // means for the side stream; a snapshot is reused two steps later -- by then its reduction has long finished
+    // (host-side query; the stream wait is the never-taken fallback)
+    const int ms_slot = (int)(c->ms_step & 1);
+    if (c->ms_buf && c->ms_used[ms_slot] && hipEventQuery(c->ms_read[ms_slot]) != hipSuccess)
+        HIPCHK(hipStreamWaitEvent(st, c->ms_read[ms_slot], 0));
+    bool isw_written = false;
+    const int launches = run_range(c, plan, a, 0, 0, prepared, dense, st, acc_stats, k4_done, se,
+                                   c->ms_buf ? c->ms_snap[ms_slot] : nullptr, &isw_written);
+    if (launches < 0) return launches;
+    c->last_step_launches = launches;
+    if (plan.partials) c->dense_armed_steps += 1;
+    if (plan.regen_recipe != 0 || plan.update_in_launch) c->store_free_steps += plan.iters;
+    if (plan.iters > 1) c->multi_iteration_launches += 1;
+    if (c->ms_buf) {
+        if ((rc = step_mode_stats(c, ms_slot, st)) != SGPMP_OK) return rc;
+        c->ms_step += 1;
     }
-    if (!fused) {
-        // (two-launch steps record their row counts too: sgpmp.h's contract is "the counts of the last in-step update", and a
-        // later fused step or a checkpoint must not see those of an older one -- advisor finding, round 5)
-        if ((rc = dense_buffers(c, &dense, temperature, false)) != SGPMP_OK) return rc;
-        HIPCHK(launch_sample(D.dtype, D.n_dof, D.traj_len, pr, seed, draw, means, P, D.particle_offset, S, eps,
-                             eps_modes, eps_mode_offset, samples, st, c->tg, prepared ? acc_stats : nullptr));
-        if (se) HIPCHK(hipEventRecord(se->ev[2], st));
-        HIPCHK(launch_cost(D.dtype, D.n_dof, D.traj_len, c->h_prog, c->d_chain, c->h_chain,
-                           samples, (long long)P * S, (long long)D.particle_offset * S, spheres, n_spheres,
-                           c->d_isw, S, pr.dt, costs, c->d_costs64, st, c->tg, &c->last_cost_kernel));
-        c->last_step_launches += 2;
-    }
-    HT(2);                                                       // the fused launch (or sampler + sweep)
-    if (se) HIPCHK(hipEventRecord(se->ev[3], st));
-    // (the update also prepares the NEXT step's importance-sampling weights -- unless, as a kernel of its own, the new
-    // means do not fit its LDS beside the weights: launch_update decides)
-    bool isw_written = tail_ran;
-    if (tail_ran) {
-        if (k4_done) HIPCHK(hipEventRecord(k4_done, st));
-    } else {
-        // per-goal mean statistics (sgpmp_set_step_mode_stats): the update kernel also leaves a snapshot of the new
-        // means for the side stream; a snapshot is reused two steps later -- by then its reduction has long finished
-        // (host-side query; the stream wait is the never-taken fallback)
-        const int slot = (int)(c->ms_step & 1);
-        if (c->ms_buf && c->ms_used[slot] && hipEventQuery(c->ms_read[slot]) != hipSuccess)
-            HIPCHK(hipStreamWaitEvent(st, c->ms_read[slot], 0));
-        const EeFoldHost eeh = {eet, c->d_chain, costs};
-        HIPCHK(launch_update(D.dtype, D.n_dof, D.traj_len, P, S, c->d_costs64, SGPMP_F64, samples, means,
-                             temperature, step_size, weights, grad, means_prev, acc_stats, st,
-                             c->tg.comm_packet_event ? k4_done : nullptr, &pr, c->d_isw,
-                             &isw_written, c->ms_buf ? c->ms_snap[slot] : nullptr,
-                             (fused && partials) ? dense.part : nullptr, dense.nnz, dense.threshold,
-                             (fused && regen.recipe != 0) ? &regen : nullptr, eet ? &eeh : nullptr));
-        if (!c->tg.comm_packet_event && k4_done) HIPCHK(hipEventRecord(k4_done, st));
-        c->last_step_launches += 1;
-        if (c->ms_buf) {
-            if ((rc = step_mode_stats(c, slot, st)) != SGPMP_OK) return rc;
-            c->ms_step += 1;
-        }
-    }
-    HT(3);                                                       // the update launch
 #ifdef SGPMP_HOST_TIMING
     g_htn += 1;
 #endif
-    c->isw_ready = isw_written; c->isw_means = means; c->isw_temperature = temperature;
-    if (se) { HIPCHK(hipEventRecord(se->ev[4], st)); se->has[3] = !tail_ran; }
+    c->isw_ready = isw_written;
+    if (se) { HIPCHK(hipEventRecord(se->ev[4], st)); se->has[3] = !plan.update_in_launch; }
     // multi-GPU: sum the statistics over all ranks on the side stream (never gates the next step)
     if (c->comm && stats) COMMCHK(comm_step_end(c->comm, stats, false));
     return SGPMP_OK;
+}
+
+extern "C" int sgpmp_step(sgpmp_ctx* c, uint64_t seed, uint64_t draw, const void* eps, int eps_modes,
+                          int eps_mode_offset, void* means, void* samples, void* costs, void* weights,
+                          void* grad, void* means_prev, const void* spheres, int n_spheres, double temperature,
+                          double step_size, double* stats, int flags, void* stream) {
+    return step_iters(c, 1, seed, draw, eps, eps_modes, eps_mode_offset, means, samples, costs, weights, grad, means_prev, spheres,
+                      n_spheres, temperature, step_size, stats, flags, stream);
 }
 
 // The loop of StochGPMP.optimize itself (planner.py:289-299: `for opt_step in range(opt_iters)`), on this side of the C ABI:
@@ -1458,44 +1450,32 @@ extern "C" int sgpmp_optimize(sgpmp_ctx* c, int opt_iters, uint64_t seed, uint64
     // the call's store-free iterations in ONE launch (fused_planar_seg.inc: PERSIST) -- a particle's workgroup needs nothing from
     // outside itself between two iterations, so what the K - 2 launch boundaries cost (4 of an iteration's 20 us there) goes.
     // Same arithmetic on the same numbers: bit-identical.  (Not with a communicator, per-step statistics of the means or the
-    // step profiler: each wants something per iteration from the host side.)
-    int inner = 0;
+    // step profiler: each wants something per iteration from the host side.  Nor where the steps run as two chains -- inside
+    // this call's bracket or the caller's own: a half would have to bring 256 workgroups, i.e. S = 64 x 512 particles.)
+    int inner = 0, per_launch = 1;
     if ((flags & SGPMP_OPT_STORE_FREE) && opt_iters >= 3 && !c->comm && !c->ms_buf && !c->profiling &&
-        means && samples && c->prior[SGPMP_PRIOR_SAMPLE].valid && finalize_program(c) == SGPMP_OK) {
-        const sgpmp_dims& D = c->dims;
-        const PriorDev& pr = c->prior[SGPMP_PRIOR_SAMPLE];
-        // (such a step is never split over the two chains: a half would have to bring 256 workgroups, i.e. S = 64 x 512 particles
-        // -- checked all the same, on the pipeline's own criterion)
-        const int P = D.num_particles, P0 = pipe_first_half(c);
-        const bool may_split = piped && !c->tg.no_step_pipeline && (long long)(P0 < P - P0 ? P0 : P - P0) * D.num_samples >= 256 * 64;
-        if (!may_split && !(pr.n_factor_modes > 0) &&
-            planar_persist_step(D.dtype, D.n_dof, D.traj_len, pr, c->h_prog, c->h_chain, P, D.particle_offset, D.num_samples, n_spheres, c->tg))
+        means && samples && c->prior[SGPMP_PRIOR_SAMPLE].valid && !(c->prior[SGPMP_PRIOR_SAMPLE].n_factor_modes > 0) &&
+        finalize_program(c) == SGPMP_OK) {
+        const StepWants wants = {false, true, true, 1};
+        const StepPlan plan = plan_range(c, c->dims.num_particles, 0, n_spheres, wants);
+        StepPlan half[2];
+        if (plan.max_iters > 1 && !plan_two_chains(c, piped || c->pipe.active, wants, plan, half)) {
             inner = opt_iters - 1;
+            per_launch = plan.max_iters;          // (a longer call takes several such launches, a single left-over iteration an ordinary store-free step)
+        }
     }
     if (piped && (rc = sgpmp_pipeline_begin(c, stream)) != SGPMP_OK) return rc;
-    // (a launch runs persist_max_iters iterations at most -- 2048: ~25 ms at BASELINE configs[1], far below anything a driver
-    // would call a hang; a longer call takes several such launches, a single left-over iteration an ordinary store-free step)
-    const long long cap = c->tg.persist_max_iters >= 2 ? c->tg.persist_max_iters : 2048;
     for (int k = 0; k < opt_iters; ++k) {
         const bool last = k == opt_iters - 1;
-        if (inner - k >= 2) {
-            // iterations k .. k + n - 1 (draws draw0 + k ...) in one launch; no statistics of theirs are formed
-            const int n = (int)((long long)(inner - k) < cap ? (long long)(inner - k) : cap);
-            c->tail_iters_next = n;
-            rc = sgpmp_step(c, seed, draw0 + (uint64_t)k, nullptr, 0, 0, means, samples, costs, weights, grad, means_prev_scratch,
-                            spheres, n_spheres, temperature, step_size, nullptr,
-                            ((k > 0 || (flags & SGPMP_STEP_MEANS_KEPT)) ? SGPMP_STEP_MEANS_KEPT : 0) | SGPMP_STEP_NO_SAMPLES, stream);
-            c->tail_iters_next = 0;
-            if (rc != SGPMP_OK) break;
-            k += n - 1;
-            continue;
-        }
+        // iterations k .. k + n - 1 (draws draw0 + k ...) in one launch where n >= 2; no statistics of theirs are formed
+        const int n = inner - k >= 2 ? (inner - k < per_launch ? inner - k : per_launch) : 1;
         const int f = ((k > 0 || (flags & SGPMP_STEP_MEANS_KEPT)) ? SGPMP_STEP_MEANS_KEPT : 0) |
-                      ((!last && (flags & SGPMP_OPT_STORE_FREE)) ? SGPMP_STEP_NO_SAMPLES : 0);
-        double* st = stats_pair ? stats_pair + (size_t)((first_slot + k) & 1) * SGPMP_STAT_SHARDS * 4 : nullptr;
-        rc = sgpmp_step(c, seed, draw0 + (uint64_t)k, nullptr, 0, 0, means, samples, costs, weights, grad,
+                      ((n > 1 || (!last && (flags & SGPMP_OPT_STORE_FREE))) ? SGPMP_STEP_NO_SAMPLES : 0);
+        double* st = stats_pair && n == 1 ? stats_pair + (size_t)((first_slot + k) & 1) * SGPMP_STAT_SHARDS * 4 : nullptr;
+        rc = step_iters(c, n, seed, draw0 + (uint64_t)k, nullptr, 0, 0, means, samples, costs, weights, grad,
                         last ? means_prev_last : means_prev_scratch, spheres, n_spheres, temperature, step_size, st, f, stream);
         if (rc != SGPMP_OK) break;
+        k += n - 1;
     }
     if (piped) {                                                 // (always closed: the chains must rejoin `stream` even after an error)
         const int rc2 = sgpmp_pipeline_end(c, stream);

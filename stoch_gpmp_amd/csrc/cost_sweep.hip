@@ -40,7 +40,7 @@
 #include "cost_device.h"
 #include "cost_host.h"
 
-// ---- host side of the kernel-argument structs (make_termk: cost_host.h, shared with traj_dense.hip)
+// ---- host side of the kernel-argument structs (make_termk, make_flat: cost_host.h)
 template <typename real>
 static ProgK<real> make_progk(const CostProgram& p) {
     ProgK<real> k;
@@ -49,181 +49,39 @@ static ProgK<real> make_progk(const CostProgram& p) {
     return k;
 }
 
-template <typename real>
-static bool make_flat(const CostProgram& p, FlatProg<real>& f) {
-    std::memset(&f, 0, sizeof(f));
-    for (int i = 0; i < p.n_terms; ++i) {
-        const TermK<real> k = make_termk<real>(p.terms[i]);
-        int* has = nullptr;
-        TermK<real>* slot = nullptr;
-        switch (k.kind) {
-            case SGPMP_COST_GP: has = &f.has_gp; slot = &f.gp; break;
-            case SGPMP_COST_GOAL_PRIOR: has = &f.has_goal; slot = &f.goal; break;
-            case SGPMP_COST_GRID: has = &f.has_grid; slot = &f.grid; break;
-            case SGPMP_COST_SELF: has = &f.has_self; slot = &f.self; break;
-            case SGPMP_COST_SPHERES: has = &f.has_sph; slot = &f.sph; f.sph_index = i; break;
-            case SGPMP_COST_EE_GOAL: continue;      // evaluated by ee_goal_kernel after the sweep
-            default: return false;
-        }
-        if (*has) return false;                      // a second term of this kind: not flat
-        *has = 1;
-        *slot = k;
-    }
-    return true;
-}
-
 #include "cost_sweep_kernel.inc"
 #include "cost_sweep_dual.inc"
 #include "fused_step.inc"
 #include "fused_planar.inc"
 #include "fused_planar_seg.inc"
 
-// Does a step qualify for a fused launch?  1: chain-code program (fused_step.inc), 2: program without forward
-// kinematics (fused_planar.inc), 0: no.
-static int fused_step_kind(int dtype, int n, int T, const PriorDev& prior, const CostProgram& h_prog,
-                           const ChainDev& h_chain, int P, int mode_offset, int S, int n_spheres,
-                           const SgpmpToggles& tg) {
+// K2 + K3 in one launch, as the plan says (step_plan.hip: plan_step has the conditions)
+hipError_t launch_fused_step(const StepPlan& plan, const StepIo& io) {
     using CCp = ChainCode_panda;
-    if (tg.no_fused_step || !prior.isotropic) return 0;
-    if (dtype == SGPMP_F64) {
-        // fp64 contexts: sampler + sweep as fused_step_f64_kernel (cost_sweep_kernel.inc: GEN) -- one wave per trajectory, lane =
-        // waypoint, the recurrence as a scan over the lanes; FLAT programs on the positions themselves (n = 2, 3) or on the chain
-        // code built with the library
-        if (T < 2 || P < 1 || S < 1 || !prior.scan64 || tg.no_flat_program) return 0;
-        if ((long long)P * S + (long long)mode_offset * S >= (1LL << 31)) return 0;
-        FlatProg<double> F;
-        if (!make_flat<double>(h_prog, F)) return 0;
-        if (F.has_goal && F.goal.rows_per_goal % S != 0) return 0;
-        if (F.has_gp && prior.dt != F.gp.dt) return 0;
-        for (int i = 0; i < h_prog.n_terms; ++i)
-            if (h_prog.terms[i].n_interp > 0) return 0;
-        if (!h_prog.needs_fk) {
-            if (F.has_self || F.has_sph || (n != 2 && n != 3)) return 0;
-            return 3;
-        }
-        if (tg.no_chain_codegen || tg.force_generic_fk || !h_chain.plan.fast || h_chain.plan.codegen_id != 1 || n != CCp::N || F.has_grid) return 0;
-        return 3;
-    }
-    if (dtype != SGPMP_F32) return 0;
-    // (S: the chain-code launch masks the rows of a particle's last group of 8 -- round 4; the planar launches want whole groups)
-    // (T: the chain-code launch masks the columns and cost lanes past T in the last chunk of 16 -- T even: 16-byte rows)
-    if (T < 2 || T % 2 != 0 || P < 1 || S < 1) return 0;
-    const bool ragged = S % SGPMP_FUSED_SPW != 0 || T % SGPMP_FUSED_TC != 0;
-    if ((long long)P * S + (long long)mode_offset * S >= (1LL << 31)) return 0;
-    FlatProg<float> F;
-    if (tg.no_flat_program || !make_flat<float>(h_prog, F)) return 0;
-    if (F.has_goal && (F.goal.rows_per_goal % S != 0 || F.goal.dim0 > SGPMP_FUSED_GOALS)) return 0;   // (a particle has one goal)
-    if (F.has_gp && (float)prior.dt != F.gp.dt) return 0;                 // IS term and GP factors share Phi
-    if (!h_prog.needs_fk && h_prog.n_ee == 0) {
-        if (ragged) return 0;
-        // no link fields: GP / goal prior / occupancy grid on the positions themselves
-        if (F.has_self || F.has_sph || (n != 2 && n != 3) || T > SGPMP_PLANAR_TMAX) return 0;
-        if (F.has_grid && n < 2) return 0;
-        return 2;
-    }
-    if (tg.no_dual_sweep || tg.no_chain_codegen || tg.force_generic_fk) return 0;
-    if (!h_chain.plan.fast || F.has_grid) return 0;
-    if (h_chain.plan.codegen_id == 1) { if (n != CCp::N) return 0; }         // the chain built with the library
-    else if (h_chain.plan.codegen_id != 2 || !h_chain.rtc || n > 7) return 0;   // ... or compiled at run time (sgpmp_set_fk_codegen)
-    if (n_spheres > SGPMP_FUSED_SPH) return 0;
-    for (int i = 0; i < h_prog.n_terms; ++i)
-        if (h_prog.terms[i].n_interp > 0) return 0;
-    if (h_chain.plan.codegen_id == 2 &&
-        !rtc_kernel((RtcChain*)h_chain.rtc, F.has_sph ? (F.sph.flags & 15) : SGPMP_FIELD_RBF, false)) return 0;   // (compiled on first use)
-    return 1;
-}
-
-bool fused_step_eligible(int dtype, int n, int T, const PriorDev& prior, const CostProgram& h_prog,
-                         const ChainDev& h_chain, int P, int mode_offset, int S, int n_spheres,
-                         const SgpmpToggles& tg) {
-    return fused_step_kind(dtype, n, T, prior, h_prog, h_chain, P, mode_offset, S, n_spheres, tg) != 0;
-}
-
-// Shape of the lane-per-sample launch (fused_planar_seg.inc): waypoints per wave, 0 when (S, T, n) does not fit.
-// Never a function of the particle count.
-static int planar_seg_len(int n, int T, int S, const SgpmpToggles& tg) {
-    if (tg.no_planar_seg || S % 64 != 0) return 0;
-    const int L = T <= 128 ? 8 : 16;
-    if (T % L != 0 || T / L > 16 || (L == 16 && n != 2)) return 0;
-    return L;
-}
-
-// Does the step run as fused_planar_seg_kernel (1024-thread workgroups, one per particle and 64 samples)?
-bool planar_seg_step(int dtype, int n, int T, const PriorDev& prior, const CostProgram& h_prog, const ChainDev& h_chain,
-                     int P, int mode_offset, int S, int n_spheres, const SgpmpToggles& tg) {
-    return fused_step_kind(dtype, n, T, prior, h_prog, h_chain, P, mode_offset, S, n_spheres, tg) == 2 &&
-           planar_seg_len(n, T, S, tg) != 0;
-}
-
-static size_t planar_seg_lds(int n, int T, int L) {
-    const int G = T / L;
-    return (size_t)G * 64 * (16 * n + 8) + (size_t)G * 64 * 20 * sizeof(float) + (size_t)G * 16;
-}
-bool planar_tail_step(int dtype, int n, int T, const PriorDev& prior, const CostProgram& h_prog, const ChainDev& h_chain,
-                      int P, int mode_offset, int S, int n_spheres, const SgpmpToggles& tg) {
-    if (!planar_seg_step(dtype, n, T, prior, h_prog, h_chain, P, mode_offset, S, n_spheres, tg)) return false;
-    const int L = planar_seg_len(n, T, S, tg);
-    return S == 64 && prior.isotropic && !tg.no_planar_tail && (long long)P * S / 64 <= (1LL << 20) &&
-           (size_t)T * 2 * n * sizeof(float) + planar_seg_lds(n, T, L) <= 160 * 1024;
-}
-// ... and can ONE launch run several of them (PERSIST)?  Instantiated for n = 2 with segments of 8 waypoints -- BASELINE
-// configs[1]'s shape: 110 vector registers.  Segments of 16 and n = 3 hold 32 / 48 waypoint values per lane: their single-step
-// launches use 118 / 114 of the 128 registers a 1024-thread workgroup's waves can have, and the loop's few carried values
-// pushed 21 / 19 registers into scratch (tools/audit_asm_loads.py refuses scratch in these kernels) -- those shapes keep one
-// launch per iteration.
-bool planar_persist_step(int dtype, int n, int T, const PriorDev& prior, const CostProgram& h_prog, const ChainDev& h_chain,
-                         int P, int mode_offset, int S, int n_spheres, const SgpmpToggles& tg) {
-    return !tg.no_persist_planar && n == 2 && planar_seg_len(n, T, S, tg) == 8 &&
-           planar_tail_step(dtype, n, T, prior, h_prog, h_chain, P, mode_offset, S, n_spheres, tg);
-}
-
-// Which rows would update_kernel have to regenerate if this step ran store-free?  1: fused_step_kernel's, 2:
-// fused_planar_seg_kernel's (*seg_len waypoints per segment), 0: the step's launch has no store-free form (the tile launch
-// fused_planar_kernel, the two-launch paths) or its costs are not complete inside the launch (ee_goal_kernel reads the rows).
-int fused_step_regen_recipe(int dtype, int n, int T, const PriorDev& prior, const CostProgram& h_prog, const ChainDev& h_chain,
-                            int P, int mode_offset, int S, int n_spheres, const SgpmpToggles& tg, int* seg_len) {
-    if (seg_len) *seg_len = 0;
-    const int kind = fused_step_kind(dtype, n, T, prior, h_prog, h_chain, P, mode_offset, S, n_spheres, tg);
-    if (kind == 0 || kind == 3 || h_prog.n_ee > 0) return 0;
-    if (kind == 1) return 1;
-    // (the lane-per-sample planar launch: built, bit-identical, and measured slower store-free at config 2 -- its update kernel is
-    // not hidden under another chain's launch, and regenerating a row costs it more than the launch saves: opt-in)
-    if (!tg.planar_store_free) return 0;
-    const int L = planar_seg_len(n, T, S, tg);
-    if (!L || (long long)P * S / 64 > (1LL << 20)) return 0;
-    if (seg_len) *seg_len = L;
-    return 2;
-}
-
-// K2 + K3 in one launch when the step qualifies; *launched says whether it did.
-hipError_t launch_fused_step(int dtype, int n, int T, const PriorDev& prior, const CostProgram& h_prog,
-                             const ChainDev& h_chain, uint64_t seed, uint64_t draw, const void* means, int P,
-                             int mode_offset, int S, void* samples, const void* spheres, int n_spheres,
-                             const void* isw, double* zero_stats, void* costs, double* costs64,
-                             hipStream_t stream, const SgpmpToggles& tg, const char** picked, bool* launched,
-                             const FusedDenseHost* dense, bool* partials_armed, RegenHost* regen, bool* tail_ran) {
-    *launched = false;
-    if (tail_ran) *tail_ran = false;
-    if (partials_armed) *partials_armed = false;
-    if (regen) std::memset(regen, 0, sizeof(*regen));
-    using CCp = ChainCode_panda;
-    const int kind = (!samples || !isw) ? 0 : fused_step_kind(dtype, n, T, prior, h_prog, h_chain, P, mode_offset, S, n_spheres, tg);
-    if (kind == 0) return hipSuccess;
-    if (kind == 3) {
+    const StepShape& sh = plan.shape;
+    const int n = sh.n, T = sh.T, S = sh.S, P = sh.P, n_spheres = sh.n_spheres;
+    const PriorDev& prior = *io.prior;
+    const CostProgram& h_prog = *io.prog;
+    const FusedDenseHost& dense = io.dense;
+    hipStream_t stream = io.stream;
+    if (plan.family == STEP_NONE || !io.samples || !io.isw) return hipErrorInvalidValue;
+    if (plan.iters > 1 && !plan.update_in_launch) return hipErrorInvalidValue;    // (several iterations: only where the launch updates)
+    auto log2_exact = [](long long v) { int s = 0; while ((1LL << s) < v && s < 62) ++s; return (1LL << s) == v ? s : -1; };
+    const long long batch = (long long)P * S, batch_offset = (long long)sh.offset * S;
+    if (plan.family == STEP_F64) {
         FlatProg<double> F;
         make_flat<double>(h_prog, F);
         const ProgK<double> PK = make_progk<double>(h_prog);
-        auto log2x = [](long long v) { int s = 0; while ((1LL << s) < v && s < 62) ++s; return (1LL << s) == v ? s : -1; };
         CostArgs<double> a;
-        a.T = T; a.chain = nullptr; a.n_links = h_chain.n_links; a.trajs = (const double*)samples;
-        a.batch = (long long)P * S; a.batch_offset = (long long)mode_offset * S;
-        a.spheres = (const double*)spheres; a.n_spheres = n_spheres;
-        a.isw = (const double*)isw; a.rows_per_particle = S; a.is_dt = prior.dt;
-        a.costs = (double*)costs; a.costs64 = costs64;
-        a.rpp_shift = log2x(S); a.rpg_shift = F.has_goal ? log2x(F.goal.rows_per_goal) : -1;
+        a.T = T; a.chain = nullptr; a.n_links = io.chain->n_links; a.trajs = (const double*)io.samples;
+        a.batch = batch; a.batch_offset = batch_offset;
+        a.spheres = (const double*)io.spheres; a.n_spheres = n_spheres;
+        a.isw = (const double*)io.isw; a.rows_per_particle = S; a.is_dt = prior.dt;
+        a.costs = (double*)io.costs; a.costs64 = io.costs64;
+        a.rpp_shift = log2_exact(S); a.rpg_shift = F.has_goal ? log2_exact(F.goal.rows_per_goal) : -1;
         GenArgs64 g;
-        g.coef = prior.iso64; g.scan = prior.scan64; g.means = (const double*)means; g.samples = (double*)samples;
-        g.seed = seed; g.draw = draw; g.mode_offset = mode_offset; g.S = S; g.zero_stats = zero_stats;
+        g.coef = prior.iso64; g.scan = prior.scan64; g.means = (const double*)io.means; g.samples = (double*)io.samples;
+        g.seed = io.seed; g.draw = io.draw; g.mode_offset = sh.offset; g.S = S; g.zero_stats = io.zero_stats;
         const size_t lds = (size_t)T * SGPMP_SCAN64_ROW * sizeof(double);
         // (few trajectories -- BASELINE configs[0] has 64 -- : one wave per workgroup, so that every wave gets a CU of its own, and
         // the lanes read their rows of the scan table straight from memory: staging 14 KB per workgroup for one or two items is a
@@ -233,169 +91,113 @@ hipError_t launch_fused_step(int dtype, int n, int T, const PriorDev& prior, con
         long long blocks = (a.batch + block / 64 - 1) / (block / 64);
         const long long cap = 256LL * 32;
         if (blocks > cap) blocks = cap;
-        const bool mixed = tg.f64_fields_f32 && h_prog.needs_fk && n_spheres <= SGPMP_SPH_LDS;
         // (+ the chain launches' store tile: a pass of 64 waypoints x d doubles per wave -- cost_sweep_kernel.inc)
         const bool store_tile = scan_lds && h_prog.needs_fk;
         const unsigned dyn = scan_lds ? (unsigned)(lds + (store_tile ? (size_t)(block / 64) * 64 * 2 * n * sizeof(double) : 0)) : 0u;
         // (SCAN_: how a big launch reads its staged scan table -- cost_sweep_kernel.inc: in one batch, or round by round)
 #define F64_LAUNCH(K_, N_, FK_, SCAN_) do { if (scan_lds) hipLaunchKernelGGL((K_<N_, FK_, SCAN_>), dim3((unsigned)blocks), dim3(block), dyn, stream, a, PK, F, g); \
                                             else hipLaunchKernelGGL((K_<N_, FK_, 0>), dim3((unsigned)blocks), dim3(block), dyn, stream, a, PK, F, g); } while (0)
-        if (h_prog.needs_fk && mixed) F64_LAUNCH(fused_step_f64_mixed_kernel, CCp::N, 1000, 2);
+        if (h_prog.needs_fk && plan.mixed) F64_LAUNCH(fused_step_f64_mixed_kernel, CCp::N, 1000, 2);
         else if (h_prog.needs_fk) F64_LAUNCH(fused_step_f64_kernel, CCp::N, 1000, 1);
         else if (n == 2) F64_LAUNCH(fused_step_f64_kernel, 2, 0, 2);
         else F64_LAUNCH(fused_step_f64_kernel, 3, 0, 2);
 #undef F64_LAUNCH
-        if (picked) *picked = mixed ? "fused_step_f64_mixed_kernel" : "fused_step_f64_kernel";
-        *launched = true;
         return hipGetLastError();
     }
     FlatProg<float> F;
     make_flat<float>(h_prog, F);
-    const long long batch = (long long)P * S, batch_offset = (long long)mode_offset * S;
-    auto log2_exact = [](long long v) { int s = 0; while ((1LL << s) < v && s < 62) ++s; return (1LL << s) == v ? s : -1; };
     CostArgs<float> a;
-    a.T = T; a.chain = nullptr; a.n_links = h_chain.n_links; a.trajs = (const float*)samples;
-    a.batch = batch; a.batch_offset = batch_offset; a.spheres = (const float*)spheres; a.n_spheres = n_spheres;
-    a.isw = (const float*)isw; a.rows_per_particle = S; a.is_dt = (float)prior.dt;
-    a.costs = (float*)costs; a.costs64 = costs64;
+    a.T = T; a.chain = nullptr; a.n_links = io.chain->n_links; a.trajs = (const float*)io.samples;
+    a.batch = batch; a.batch_offset = batch_offset; a.spheres = (const float*)io.spheres; a.n_spheres = n_spheres;
+    a.isw = (const float*)io.isw; a.rows_per_particle = S; a.is_dt = (float)prior.dt;
+    a.costs = (float*)io.costs; a.costs64 = io.costs64;
     a.rpp_shift = log2_exact(S);
     a.rpg_shift = F.has_goal ? log2_exact(F.goal.rows_per_goal) : -1;
+    const bool chain_code = plan.family == STEP_CHAIN || plan.family == STEP_CHAIN_RTC;
     FusedArgs fs;
-    fs.coef = prior.iso32; fs.coefp = prior.iso32p; fs.means = (const float*)means; fs.samples = (float*)samples;
-    fs.seed = seed; fs.draw = draw; fs.mode_offset = mode_offset; fs.S = S;
+    fs.coef = prior.iso32; fs.coefp = prior.iso32p; fs.means = (const float*)io.means; fs.samples = (float*)io.samples;
+    fs.seed = io.seed; fs.draw = io.draw; fs.mode_offset = sh.offset; fs.S = S;
     fs.gpp = (S + SGPMP_FUSED_SPW - 1) / SGPMP_FUSED_SPW; fs.gpp_shift = log2_exact(fs.gpp);
     fs.nitems = (long long)P * fs.gpp;
-    fs.zero_stats = zero_stats;
-    fs.part = nullptr; fs.nnz_prev = nullptr; fs.nnz_threshold = 0u; fs.inv_temperature = 0.f;
+    fs.zero_stats = io.zero_stats;
+    fs.part = nullptr; fs.nnz_prev = dense.nnz; fs.nnz_threshold = 0u; fs.inv_temperature = 0.f;
     fs.nostore = 0; fs.store_threshold = 0u;
     std::memset(&fs.tail, 0, sizeof(fs.tail));
-    if (dense && dense->nnz) fs.nnz_prev = dense->nnz;
-    // softmax partials for the dense-weight regime of the update: chain-code launch whose costs are complete inside it
-    if (kind == 1 && dense && dense->part && dense->nnz && h_prog.n_ee == 0 && !tg.no_dense_partials && (T * 2 * n) % 4 == 0) {
-        fs.part = dense->part; fs.nnz_threshold = dense->threshold;
-        fs.inv_temperature = (float)(1. / dense->temperature);
-        if (partials_armed) *partials_armed = true;
+    if (plan.partials) {                          // softmax partials for the dense-weight regime of the update
+        if (!dense.part || !dense.nnz) return hipErrorInvalidValue;
+        fs.part = dense.part; fs.nnz_threshold = dense.threshold;
+        fs.inv_temperature = (float)(1. / dense.temperature);
     }
-    // store-free step: the caller does not read this step's samples and the update behind the launch can regenerate rows
-    if (dense && dense->nostore && dense->nnz && regen) {
-        int L = 0;
-        const int recipe = fused_step_regen_recipe(dtype, n, T, prior, h_prog, h_chain, P, mode_offset, S, n_spheres, tg, &L);
-        // ... and regenerating pays: update_kernel's regeneration is a dependent chain of ~6.5 us per particle (T = 64) that a small
-        // step cannot hide, while what the launch saves grows with the bytes it does not write.  Measured break-even on MI355X
-        // (tools/store_free_sizes.py, profiles/r05/store_free_sizes.txt: Panda, S = 64 .. 512, T = 32 and 64, P = 16 .. 2048):
-        // 176 MB of samples per step at T = 64, ~88 MB at T = 32 -- i.e. 2.75 MB per waypoint; below it a store-free step ran
-        // 4 .. 20 % SLOWER than a storing one, so the step stores (same results either way: the choice is a function of the shape).
-        const long long waypoint_bytes = (long long)dense->particles_total * S * 2 * n * (long long)sizeof(float);
-        const long long min_bytes = tg.store_free_min_bytes > 0 ? tg.store_free_min_bytes : SGPMP_STORE_FREE_BREAK_EVEN;
-        if (recipe != 0 && waypoint_bytes >= min_bytes && update_regen_rows(dtype, n, T, S, recipe) > 0) {
-            fs.nostore = 1; fs.store_threshold = dense->store_threshold;
-            regen->recipe = recipe; regen->L = L; regen->seed = seed; regen->draw = draw; regen->mode_offset = mode_offset;
-            regen->coef = recipe == 1 ? prior.iso32p : prior.iso32;
-            regen->pre = recipe == 2 ? prior.slabpre + (size_t)(L == 8 ? 3 : 4) * T * 4 : nullptr;
-            regen->store_threshold = dense->store_threshold;
-        }
+    if (plan.regen_recipe != 0) {                 // store-free step: the update behind the launch regenerates rows
+        if (!dense.nnz) return hipErrorInvalidValue;
+        fs.nostore = 1; fs.store_threshold = dense.store_threshold;
     }
-    const long long nitems = kind == 1 ? fs.nitems : batch / SGPMP_FUSED_SPW;
+    const long long nitems = chain_code ? fs.nitems : batch / SGPMP_FUSED_SPW;
     long long blocks = (nitems + 3) / 4;
-    // one item per wave measured fastest at config 3 (4096 workgroups 0.216 ms/iteration, 2048: 0.219,
-    // 1024: 0.227): the per-workgroup set-up is small and the hardware dispatcher balances better than
-    // a grid-stride loop; the loop stays for batches beyond 2^20 items and for the k3_blocks switch
-    long long cap = 1LL << 18;
-    if (tg.k3_blocks > 0) cap = tg.k3_blocks;
-    if (blocks > cap) blocks = cap;
-    if (kind == 2) {
-        // lane = sample, wave = time segment (fused_planar_seg.inc) where the shape allows; picked from (S, T, n) alone
-        {
-            const int L = planar_seg_len(n, T, S, tg), G = L ? T / L : 0;
-            const long long wgs = batch / 64;
-            if (L && wgs <= (1LL << 20)) {
-                size_t lds = planar_seg_lds(n, T, L);
-                fs.gpp = S / 64; fs.gpp_shift = log2_exact(fs.gpp);
-                // Store-free step of a problem whose particles have exactly one workgroup's 64 samples: the UPDATE runs inside the
-                // launch (seg_update) -- no sample store, no update_kernel, no regeneration: one launch per iteration
-                const bool upd = dense && dense->nostore && dense->tail_done && tail_ran && S == 64 && prior.isotropic && !tg.no_planar_tail &&
-                                 (size_t)T * 2 * n * sizeof(float) + lds <= 160 * 1024;
-                if (upd) {
-                    SegTail& t = fs.tail;
-                    t.done = dense->tail_done; t.acc = dense->tail_acc; t.stats_out = dense->stats_out;
-                    t.means = (float*)const_cast<void*>(means); t.weights = (float*)dense->weights; t.grad = (float*)dense->grad;
-                    t.means_prev = (float*)dense->means_prev; t.isw_next = (float*)const_cast<void*>(isw); t.nnz_out = dense->nnz;
-                    t.Qinv = prior.Qinv; t.ks = prior.ks; t.kg = prior.kg; t.dt = prior.dt;
-                    t.temperature = dense->temperature; t.step_size = dense->step_size; t.P = P;
-                    t.iters = dense->tail_iters > 1 ? dense->tail_iters : 1;
-                    if (t.iters > 1 && !(n == 2 && L == 8)) return hipErrorInvalidValue;    // (planar_persist_step: the caller asks first)
-                    if (t.iters > 1) { t.done = nullptr; t.stats_out = nullptr; }    // (several iterations in this launch: no statistics)
-                    fs.nostore = 1; fs.store_threshold = 0xffffffffu;
-                    fs.zero_stats = nullptr;                      // (the launch's last particle writes the statistics)
-                    lds += (size_t)T * 2 * n * sizeof(float);
-                    if (regen) regen->recipe = 0;                 // (nothing left for update_kernel to regenerate: there is no update_kernel)
-                    *tail_ran = true;
-                }
-                const float* tab = prior.slabpre + (size_t)(L == 8 ? 3 : 4) * T * 4;
-                const bool persist = upd && fs.tail.iters > 1;
-#define SEG_LAUNCH(NN, LL) do { if (upd) hipLaunchKernelGGL((fused_planar_seg_kernel<NN, LL, true>), dim3((unsigned)wgs), dim3(64 * G), (unsigned)lds, stream, a, F, fs, tab); \
-                                 else hipLaunchKernelGGL((fused_planar_seg_kernel<NN, LL, false>), dim3((unsigned)wgs), dim3(64 * G), (unsigned)lds, stream, a, F, fs, tab); } while (0)
-                if (persist) hipLaunchKernelGGL((fused_planar_seg_kernel<2, 8, true, true>), dim3((unsigned)wgs), dim3(64 * G), (unsigned)lds, stream, a, F, fs, tab);
-                else if (n == 2) { if (L == 8) SEG_LAUNCH(2, 8); else SEG_LAUNCH(2, 16); }
-                else SEG_LAUNCH(3, 8);
-#undef SEG_LAUNCH
-                if (picked) *picked = "fused_planar_seg_kernel";
-                *launched = true;
-                return hipGetLastError();
-            }
+    if (blocks > plan.block_cap) blocks = plan.block_cap;
+    if (plan.family == STEP_PLANAR_SEG) {
+        const int L = plan.L, G = T / L;
+        const long long wgs = batch / 64;
+        const bool upd = plan.update_in_launch;
+        fs.gpp = S / 64; fs.gpp_shift = log2_exact(fs.gpp);
+        if (upd) {
+            if (!dense.tail_done) return hipErrorInvalidValue;
+            SegTail& t = fs.tail;
+            t.done = dense.tail_done; t.acc = dense.tail_acc; t.stats_out = dense.stats_out;
+            t.means = (float*)const_cast<void*>(io.means); t.weights = (float*)dense.weights; t.grad = (float*)dense.grad;
+            t.means_prev = (float*)dense.means_prev; t.isw_next = (float*)const_cast<void*>(io.isw); t.nnz_out = dense.nnz;
+            t.Qinv = prior.Qinv; t.ks = prior.ks; t.kg = prior.kg; t.dt = prior.dt;
+            t.temperature = dense.temperature; t.step_size = dense.step_size; t.P = P;
+            t.iters = plan.iters;
+            if (t.iters > 1) { t.done = nullptr; t.stats_out = nullptr; }    // (several iterations in this launch: no statistics)
+            fs.nostore = 1; fs.store_threshold = 0xffffffffu;
+            fs.zero_stats = nullptr;                      // (the launch's last particle writes the statistics)
         }
-        if (n == 2) hipLaunchKernelGGL((fused_planar_kernel<2>), dim3((unsigned)blocks), dim3(256), 0, stream, a, F, fs);
-        else hipLaunchKernelGGL((fused_planar_kernel<3>), dim3((unsigned)blocks), dim3(256), 0, stream, a, F, fs);
-        if (picked) *picked = "fused_planar_kernel";
-        *launched = true;
+        const float* tab = prior.slabpre + (size_t)plan.seg_table * T * 4;
+        const unsigned lds = plan.seg_lds;
+#define SEG_LAUNCH(NN, LL) do { if (upd) hipLaunchKernelGGL((fused_planar_seg_kernel<NN, LL, true>), dim3((unsigned)wgs), dim3(64 * G), lds, stream, a, F, fs, tab); \
+                                 else hipLaunchKernelGGL((fused_planar_seg_kernel<NN, LL, false>), dim3((unsigned)wgs), dim3(64 * G), lds, stream, a, F, fs, tab); } while (0)
+        if (plan.iters > 1) {
+            if (n != 2 || L != 8) return hipErrorInvalidValue;     // (PERSIST is instantiated for this shape alone)
+            hipLaunchKernelGGL((fused_planar_seg_kernel<2, 8, true, true>), dim3((unsigned)wgs), dim3(64 * G), lds, stream, a, F, fs, tab);
+        }
+        else if (n == 2) { if (L == 8) SEG_LAUNCH(2, 8); else SEG_LAUNCH(2, 16); }
+        else SEG_LAUNCH(3, 8);
+#undef SEG_LAUNCH
         return hipGetLastError();
     }
-    const int ft = F.has_sph ? (F.sph.flags & 15) : SGPMP_FIELD_RBF;
-    // a SMALL step -- fewer items than SIMDs: every wave of the one-wave-per-item launch would sit alone on its SIMD for as long as
-    // one item takes one wave (~20 us) -- goes out with one WORKGROUP per item instead, its four waves on the item's chunks side
-    // by side (fused_step.inc: LAT; same samples and costs, bit for bit).  Up to two workgroups per CU for shapes on the launch's
-    // 8 x 16 grid (253 registers, 57 KB of LDS: two per SIMD set), one for the others (the masked instantiation needs 262 registers):
-    // beyond, a second round of workgroups costs what the other launch does in one (tools/small_step_sizes.py).
-    const bool srag = S % SGPMP_FUSED_SPW != 0 || T % SGPMP_FUSED_TC != 0;           // (the instantiation fused_step_kernel would take)
-    const long long small_items = tg.small_step_items > 0 ? tg.small_step_items : srag ? 256 : 512;
-    // (judged on the WHOLE problem -- all ranks' particles, both halves of a pipelined step -- so that a shard takes the launch its
-    // unsharded run takes)
-    const long long items_global = (long long)(dense && dense->particles_global > 0 ? dense->particles_global : P) * fs.gpp;
-    const bool small = !tg.no_small_step && items_global <= small_items && (T + SGPMP_FUSED_TC - 1) / SGPMP_FUSED_TC <= 16;
-    if (h_chain.plan.codegen_id == 2) {           // this chain's kernels were compiled at run time (chain_rtc.hip)
-        hipFunction_t f = rtc_kernel((RtcChain*)h_chain.rtc, ft, false, srag, small);
-        if (!f) return hipSuccess;                // (not launched: the caller takes the two-launch path)
+    if (plan.family == STEP_PLANAR_TILE) {
+        if (n == 2) hipLaunchKernelGGL((fused_planar_kernel<2>), dim3((unsigned)blocks), dim3(256), 0, stream, a, F, fs);
+        else hipLaunchKernelGGL((fused_planar_kernel<3>), dim3((unsigned)blocks), dim3(256), 0, stream, a, F, fs);
+        return hipGetLastError();
+    }
+    const int ft = plan.field_type;
+    const bool rag = plan.ragged, small = plan.small;
+    // the launch sizes the sphere / state tables (dynamic LDS): 30.7 KB of tiles + these per workgroup, five workgroups per CU while
+    // they stay under 2 KB
+    const size_t dyn = fused_wave_dyn_lds(n_spheres, F.has_goal ? F.goal.dim0 : 0);
+    if (plan.family == STEP_CHAIN_RTC) {           // this chain's kernels were compiled at run time (chain_rtc.hip)
+        if (!plan.rtc_fn) return hipErrorInvalidValue;
         void* args[] = {&a, &F, &fs};
-        const hipError_t e = rtc_launch(f, small ? (unsigned)fs.nitems : (unsigned)blocks, (unsigned)fused_wave_dyn_lds(n_spheres, F.has_goal ? F.goal.dim0 : 0), stream, args, nullptr);
-        if (picked) *picked = small ? "fused_step_small_kernel (run-time chain code)" : "fused_step_kernel (run-time chain code)";
-        *launched = e == hipSuccess;
-        return e;
+        return rtc_launch(plan.rtc_fn, small ? (unsigned)fs.nitems : (unsigned)blocks, (unsigned)dyn, stream, args, nullptr);
     }
 #ifndef SGPMP_FUSED_EXTRA_LDS   // occupancy diagnostic: unused bytes per workgroup, e.g. 8000 -> four workgroups per CU instead of five
 #define SGPMP_FUSED_EXTRA_LDS 0
 #endif
-    // the launch sizes the sphere / state tables (dynamic LDS): 30.7 KB of tiles + these per workgroup, five workgroups per CU while
-    // they stay under 2 KB
-    const size_t dyn = fused_wave_dyn_lds(n_spheres, F.has_goal ? F.goal.dim0 : 0);
-    // S, T off the launch's grid of 8 rows x 16 waypoints: the instantiation with the masks (fused_step.inc: RAG)
     if (small) {
 #define SMALL_LAUNCH(FT_, RAG_) hipLaunchKernelGGL((fused_step_small_kernel<CCp::N, CCp, FT_, RAG_>), dim3((unsigned)fs.nitems), dim3(256), (unsigned)dyn, stream, a, F, fs)
-        if (ft == SGPMP_FIELD_RBF) { if (srag) SMALL_LAUNCH(SGPMP_FIELD_RBF, true); else SMALL_LAUNCH(SGPMP_FIELD_RBF, false); }
-        else if (ft == SGPMP_FIELD_SDF) { if (srag) SMALL_LAUNCH(SGPMP_FIELD_SDF, true); else SMALL_LAUNCH(SGPMP_FIELD_SDF, false); }
-        else { if (srag) SMALL_LAUNCH(SGPMP_FIELD_OCCUPANCY, true); else SMALL_LAUNCH(SGPMP_FIELD_OCCUPANCY, false); }
+        if (ft == SGPMP_FIELD_RBF) { if (rag) SMALL_LAUNCH(SGPMP_FIELD_RBF, true); else SMALL_LAUNCH(SGPMP_FIELD_RBF, false); }
+        else if (ft == SGPMP_FIELD_SDF) { if (rag) SMALL_LAUNCH(SGPMP_FIELD_SDF, true); else SMALL_LAUNCH(SGPMP_FIELD_SDF, false); }
+        else { if (rag) SMALL_LAUNCH(SGPMP_FIELD_OCCUPANCY, true); else SMALL_LAUNCH(SGPMP_FIELD_OCCUPANCY, false); }
 #undef SMALL_LAUNCH
-        if (picked) *picked = "fused_step_small_kernel";
-        *launched = true;
         return hipGetLastError();
     }
+    // S, T off the launch's grid of 8 rows x 16 waypoints: the instantiation with the masks (fused_step.inc: RAG)
 #define FUSED_LAUNCH(FT_, RAG_) hipExtLaunchKernelGGL((fused_step_kernel<CCp::N, CCp, FT_, RAG_>), dim3((unsigned)blocks), dim3(256), (unsigned)dyn + SGPMP_FUSED_EXTRA_LDS, stream, (hipEvent_t) nullptr, (hipEvent_t) nullptr, 0u, a, F, fs)
-    const bool rag = S % SGPMP_FUSED_SPW != 0 || T % SGPMP_FUSED_TC != 0;
     if (ft == SGPMP_FIELD_RBF) { if (rag) FUSED_LAUNCH(SGPMP_FIELD_RBF, true); else FUSED_LAUNCH(SGPMP_FIELD_RBF, false); }
     else if (ft == SGPMP_FIELD_SDF) { if (rag) FUSED_LAUNCH(SGPMP_FIELD_SDF, true); else FUSED_LAUNCH(SGPMP_FIELD_SDF, false); }
     else { if (rag) FUSED_LAUNCH(SGPMP_FIELD_OCCUPANCY, true); else FUSED_LAUNCH(SGPMP_FIELD_OCCUPANCY, false); }
 #undef FUSED_LAUNCH
-    if (picked) *picked = "fused_step_kernel";
-    *launched = true;
     return hipGetLastError();
 }
 

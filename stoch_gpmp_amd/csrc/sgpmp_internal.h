@@ -216,21 +216,17 @@ struct FusedDenseHost {
     unsigned* nnz;                // [P] rows with weight in each particle's previous update
     unsigned threshold;           // partials for particles with nnz above it
     double temperature;
-    int nostore;                  // the caller does not need this step's samples (SGPMP_STEP_NO_SAMPLES) and the update can regenerate rows
-    unsigned store_threshold;     // ... rows are then stored for particles with nnz above it only
-    int particles_total;          // particles of the whole step (a pipelined step launches halves): the size a regenerating store-free step is judged on
-    int particles_global;         // ... of all ranks (sgpmp_dims::num_particles_global): the size the small-step launch is judged on
-    // the update INSIDE fused_planar_seg_kernel (store-free steps, S = 64; fused_planar_seg.inc: seg_update) -- what update_kernel
-    // would have been given; tail_done == null: not offered (per-step mean statistics, ...)
+    unsigned store_threshold;     // store-free steps: rows are stored for particles with nnz above it only
+    // the update INSIDE fused_planar_seg_kernel (StepPlan::update_in_launch; fused_planar_seg.inc: seg_update) -- what update_kernel
+    // would have been given
     unsigned* tail_done;          // finished-particle counter of this launch (zero between launches)
     double* tail_acc;             // [SGPMP_STAT_SHARDS][4] statistics accumulators (zero between launches)
     double* stats_out;            // the step's statistics buffer or null
     void* weights; void* grad; void* means_prev;   // K4's optional outputs (context dtype)
     double step_size;
-    int tail_iters;               // > 1: the launch runs that many store-free iterations itself (fused_planar_seg.inc: PERSIST; sgpmp_optimize)
 };
 // bytes of one waypoint of all samples of a step above which a regenerating store-free step is faster than a storing one
-// (cost_sweep.hip: launch_fused_step has the measurement)
+// (step_plan.hip: plan_step has the measurement)
 #define SGPMP_STORE_FREE_BREAK_EVEN 2800000LL
 // The step's end-effector goal term evaluated by update_kernel itself (update_common.h: EeFold) instead of ee_goal_kernel
 struct EeFoldHost {
@@ -249,35 +245,74 @@ struct RegenHost {
     unsigned store_threshold;
 };
 int update_regen_rows(int dtype, int n, int T, int S, int recipe);   // rows per round update_kernel can regenerate; 0: not this shape
-// K2 + K3 fused (cost_sweep.hip / fused_step.inc): launches only when the step qualifies (*launched)
-hipError_t launch_fused_step(int dtype, int n, int T, const PriorDev& prior, const CostProgram& h_prog,
-                             const ChainDev& h_chain, uint64_t seed, uint64_t draw, const void* means, int P,
-                             int mode_offset, int S, void* samples, const void* spheres, int n_spheres,
-                             const void* isw, double* zero_stats, void* costs, double* costs64,
-                             hipStream_t stream, const SgpmpToggles& tg, const char** picked, bool* launched,
-                             const FusedDenseHost* dense = nullptr, bool* partials_armed = nullptr, RegenHost* regen = nullptr,
-                             bool* tail_ran = nullptr);   // *tail_ran: the launch also updated its particles (no update_kernel behind it)
-// the recipe update_kernel would need to regenerate this step's rows (0: the step's launch cannot run store-free)
-int fused_step_regen_recipe(int dtype, int n, int T, const PriorDev& prior, const CostProgram& h_prog, const ChainDev& h_chain,
-                            int P, int mode_offset, int S, int n_spheres, const SgpmpToggles& tg, int* seg_len);
-bool planar_seg_step(int dtype, int n, int T, const PriorDev& prior, const CostProgram& h_prog, const ChainDev& h_chain,
-                     int P, int mode_offset, int S, int n_spheres, const SgpmpToggles& tg);
-// ... and would a store-free step of it run its update inside the launch (one launch per iteration; what PERSIST extends)?
-bool planar_tail_step(int dtype, int n, int T, const PriorDev& prior, const CostProgram& h_prog, const ChainDev& h_chain,
-                      int P, int mode_offset, int S, int n_spheres, const SgpmpToggles& tg);
-// ... and can one launch run SEVERAL such steps (FusedDenseHost::tail_iters > 1)?
-bool planar_persist_step(int dtype, int n, int T, const PriorDev& prior, const CostProgram& h_prog, const ChainDev& h_chain,
-                         int P, int mode_offset, int S, int n_spheres, const SgpmpToggles& tg);
-// does the step qualify for the fused launch? (same conditions, no launch)
-bool fused_step_eligible(int dtype, int n, int T, const PriorDev& prior, const CostProgram& h_prog,
-                         const ChainDev& h_chain, int P, int mode_offset, int S, int n_spheres,
-                         const SgpmpToggles& tg);
+bool update_ee_fold_fits(int dtype, int n, int T, int S);
+
+// ---------------------------------------------------------------------------------- the step's launches (step_plan.hip)
+// ONE decision per launch sequence: which kernels a particle range's step runs.  plan_step is a function of its arguments
+// alone (apart from the lookup of a run-time chain's kernel, compiled on first use: no device call, no context), so the
+// choice is a function of the shape -- the same in every run, as one optimize(K) call or K calls, sharded or not.
+struct StepShape {
+    int dtype, n, T, S, n_spheres;
+    int P, offset;                // the particle range the sequence runs and the global index of its particle 0
+    int particles_total;          // particles of the whole step (a two-chain step launches halves): what a regenerating store-free step is judged on
+    int particles_global;         // ... of all ranks: what the small-step launch is judged on
+};
+struct StepWants {                // what the caller offers
+    bool eps;                     // the caller brings the noise: sampler + sweep
+    bool no_samples;              // SGPMP_STEP_NO_SAMPLES: nobody reads this step's samples
+    bool update_in_launch_ok;     // nothing wants update_kernel's own outputs (per-step mean statistics do)
+    int iters;                    // iterations asked of ONE launch (sgpmp_optimize; 1 otherwise)
+};
+enum StepFamily { STEP_NONE = 0, STEP_CHAIN, STEP_CHAIN_RTC, STEP_PLANAR_TILE, STEP_PLANAR_SEG, STEP_F64 };
+enum StepEe { STEP_EE_NONE = 0, STEP_EE_FOLD, STEP_EE_LAUNCH };
+struct StepPlan {
+    StepShape shape;
+    int family;                   // STEP_NONE: sampler + sweep as launches of their own
+    bool ragged;                  // chain code: S, T off the launch's grid of 8 rows x 16 waypoints (the masked instantiation)
+    bool small;                   // chain code: one WORKGROUP per item (fused_step_small_kernel)
+    bool mixed;                   // fp64: link fields on the packed-fp32 code
+    int field_type;               // chain code: SGPMP_FIELD_* of the sphere term
+    int L;                        // planar: waypoints per wave of the lane-per-sample launch the SHAPE allows (0: none); the launch is
+                                  // STEP_PLANAR_SEG when its grid fits too
+    int seg_table;                // ... and its table of PriorDev::slabpre (3: segments of 8, 4: of 16)
+    unsigned seg_lds;             // STEP_PLANAR_SEG: dynamic LDS of the launch (with the update's share when it runs inside)
+    hipFunction_t rtc_fn;         // STEP_CHAIN_RTC: the kernel
+    long long block_cap;          // workgroups of the grid-stride launches at most
+    bool partials;                // the launch leaves softmax partials for the update (FusedDenseHost::part must be there)
+    int regen_recipe;             // store-free step whose update_kernel regenerates rows: RegenHost::recipe (0: the step stores, or has no update_kernel)
+    bool update_in_launch;        // the launch updates its particles itself: no update_kernel behind it
+    int max_iters;                // iterations one such launch may carry (1, or the PERSIST cap)
+    int iters;                    // ... and carries: StepWants::iters where the plan can (the caller compares), else 1
+    int ee;                       // StepEe: the end-effector goal term(s) of a fused step
+    const char* kernel;           // what sgpmp_last_cost_kernel reports
+};
+StepPlan plan_step(const StepShape& shape, const StepWants& wants, const PriorDev& prior, const CostProgram& prog,
+                   const ChainDev& chain, const SgpmpToggles& tg);
+// what update_kernel is told behind a launch of this plan (recipe 0: nothing to regenerate)
+static inline RegenHost plan_regen(const StepPlan& plan, const PriorDev& prior, uint64_t seed, uint64_t draw, unsigned store_threshold) {
+    RegenHost r = {};
+    if (plan.regen_recipe == 0) return r;
+    r.recipe = plan.regen_recipe; r.L = r.recipe == 2 ? plan.L : 0; r.seed = seed; r.draw = draw; r.mode_offset = plan.shape.offset;
+    r.coef = r.recipe == 1 ? prior.iso32p : prior.iso32;
+    r.pre = r.recipe == 2 ? prior.slabpre + (size_t)plan.seg_table * plan.shape.T * 4 : nullptr;
+    r.store_threshold = store_threshold;
+    return r;
+}
+struct StepIo {
+    const PriorDev* prior; const CostProgram* prog; const ChainDev* chain;
+    uint64_t seed, draw;
+    const void* means; void* samples; const void* spheres; const void* isw;
+    double* zero_stats; void* costs; double* costs64;
+    hipStream_t stream;
+    FusedDenseHost dense;
+};
+// K2 + K3 fused (cost_sweep.hip / fused_step.inc): enqueues exactly what the plan says (never a plan of STEP_NONE)
+hipError_t launch_fused_step(const StepPlan& plan, const StepIo& io);
 
 hipError_t launch_is_weights(int dtype, int n, int T, const PriorDev& prior, const void* means,
                              int n_particles, double temperature, void* out, double* zero_stats,
                              hipStream_t stream);
 
-bool update_ee_fold_fits(int dtype, int n, int T, int S);
 hipError_t launch_update(int dtype, int n, int T, int P, int S, const void* costs, int costs_dtype,
                          const void* samples, void* means, double temperature, double step_size,
                          void* weights, void* grad, void* means_prev, double* stats,

@@ -14,6 +14,7 @@
 
 extern "C" int stub_hip_live_objects(void);
 extern "C" int stub_launch_log(int i, unsigned long long* draw, int* iters);   // stub_launchers.cpp: every fused launch's (draw, iterations)
+extern "C" void stub_launch_log_range(int i, int* first, int* P);              // ... and its particle range
 extern "C" void stub_launch_log_clear();
 static int g_multi = 0;                                // launches of several iterations seen by the checks below
 extern "C" int hipMalloc(void**, size_t);
@@ -223,6 +224,51 @@ static void run_planner(int n, int T, int P, int P_global, int offset, int S, in
     sgpmp_destroy(c);
 }
 
+// sgpmp_optimize(K, SGPMP_OPT_STORE_FREE) WITHOUT SGPMP_OPT_PIPELINE inside the caller's own sgpmp_pipeline_begin .. _end, at a
+// shape whose halves qualify for two chains (n = 2, T = 16, S = 64, P = 512): a launch of several iterations and a two-chain
+// step exclude each other, and the call must decide that on the bracket it RUNS in -- it once planned K - 1 iterations for a
+// launch the step then split and ran once (advisor finding, round 6).  Whatever the launches (STUB_FUSED / _TAIL / _PERSIST):
+// every iteration's draw reaches every particle exactly once.
+static void run_bracketed_optimize() {
+    const int n = 2, T = 16, P = 512, S = 64, G = 2, d = 2 * n;
+    const size_t M = (size_t)T * d, w = 4;
+    sgpmp_dims dims = {n, T, P, 0, P, S, G, P / G, SGPMP_F32, 0};
+    sgpmp_ctx* c = nullptr;
+    CHECK(sgpmp_create(&dims, &c));
+    const double ss[2] = {1e-3, 1e-3}, sg[2] = {0.8, 0.1}, sgoal[2] = {0.1, 0.07};
+    CHECK(sgpmp_set_priors(c, 0.05, ss, sg, sgoal, nullptr));
+    std::vector<double> start(d, 0.1), goals((size_t)G * d, 0.3);
+    sgpmp_cost_desc descs[2];
+    std::memset(descs, 0, sizeof(descs));
+    descs[0].kind = SGPMP_COST_GP; descs[0].flags = SGPMP_FLAG_GP_START; descs[0].sigma = 7e-4; descs[0].sigma2 = 1e-4; descs[0].dt = 0.05; descs[0].data = start.data();
+    descs[1].kind = SGPMP_COST_GOAL_PRIOR; descs[1].sigma = 20.; descs[1].data = goals.data(); descs[1].dim0 = G; descs[1].dim1 = (P / G) * S;
+    CHECK(sgpmp_set_costs(c, descs, 2));
+    Dev means(P * M * w), samples((size_t)P * S * M * w), costs((size_t)P * S * w), weights((size_t)P * S * w), grad(P * M * w), prev(P * M * w), prev_last(P * M * w);
+    Dev stats2(sizeof(double) * 2 * SGPMP_STAT_SHARDS * 4);
+    const unsigned long long draw0 = 500;
+    for (int K : {3, 9}) {
+        CHECK(sgpmp_pipeline_begin(c, nullptr));
+        stub_launch_log_clear();
+        CHECK(sgpmp_optimize(c, K, 7, draw0, means.p, samples.p, costs.p, weights.p, grad.p, prev.p, prev_last.p, nullptr, 0, 1.0, 0.1,
+                             (double*)stats2.p, 0, SGPMP_OPT_STORE_FREE, nullptr));
+        CHECK(sgpmp_pipeline_end(c, nullptr));
+        unsigned long long dr = 0; int it = 0, first = 0, Pn = 0;
+        const int nl = stub_launch_log(-1, &dr, &it);
+        std::vector<int> seen((size_t)K * P, 0);
+        for (int i = 0; i < nl; ++i) {
+            stub_launch_log(i, &dr, &it);
+            stub_launch_log_range(i, &first, &Pn);
+            if (dr < draw0 || dr + (unsigned long long)it > draw0 + (unsigned long long)K || first < 0 || first + Pn > P) {
+                std::fprintf(stderr, "bracketed optimize(K=%d): launch %d has draws %llu x %d on particles %d + %d\n", K, i, dr, it, first, Pn); std::exit(8);
+            }
+            for (int k = 0; k < it; ++k) for (int q = first; q < first + Pn; ++q) seen[(size_t)(dr - draw0 + k) * P + q] += 1;
+        }
+        for (size_t i = 0; nl > 0 && i < seen.size(); ++i)
+            if (seen[i] != 1) { std::fprintf(stderr, "bracketed optimize(K=%d): draw %llu reached particle %d %d times\n", K, draw0 + i / P, (int)(i % P), seen[i]); std::exit(8); }
+    }
+    sgpmp_destroy(c);
+}
+
 int main() {
     EXPECT(sgpmp_create(nullptr, nullptr), SGPMP_EINVAL);
     sgpmp_dims bad = {9, 8, 1, 0, 1, 1, 1, 1, SGPMP_F32, 0};
@@ -238,6 +284,7 @@ int main() {
     run_planner(3, 16, 5, 40, 35, 8, 1, SGPMP_F32, comm, false, 11);        // the last shard of a ragged split
     run_planner(7, 16, 1024, 1024, 0, 8, 1, SGPMP_F32, comm, false, 10);      // big enough for two particle-half chains
     run_planner(7, 16, 0, 3, 3, 8, 1, SGPMP_F32, comm, true, 10);             // an empty shard still joins the collectives
+    run_bracketed_optimize();
     const int live = stub_hip_live_objects();
     if (live != 0) { std::fprintf(stderr, "%d streams / events / device buffers outlived their contexts\n", live); return 7; }
     std::printf("MULTI_ITERATION_LAUNCHES %d\n", g_multi);

@@ -64,61 +64,51 @@ hipError_t launch_cost(int dtype, int n, int T, const CostProgram&, const ChainD
 }
 bool update_ee_fold_fits(int, int, int, int S) { return S <= 4096; }
 int update_regen_rows(int dtype, int, int T, int, int recipe) { return dtype == SGPMP_F32 && T % 2 == 0 && recipe == 1 ? 4 : 0; }
-int fused_step_regen_recipe(int dtype, int n, int T, const PriorDev& pr, const CostProgram& prog, const ChainDev& ch, int P, int off, int S, int ns,
-                            const SgpmpToggles& tg, int* seg_len) {
-    if (seg_len) *seg_len = 0;
-    return fused_step_eligible(dtype, n, T, pr, prog, ch, P, off, S, ns, tg) && prog.n_ee == 0 ? 1 : 0;
+// The ONE decision (the real one: csrc/step_plan.hip, held to its table by plan_table.cpp): a chain-code-like fused step under
+// STUB_FUSED=1; STUB_TAIL=1: as if a store-free step's launch updated its particles itself (fused_planar_seg.inc: seg_update);
+// STUB_PERSIST=1 (with STUB_TAIL): as if that launch could run several iterations (PERSIST) -- sgpmp_optimize's chunking of a
+// call is then exercised on the host
+StepPlan plan_step(const StepShape& sh, const StepWants& w, const PriorDev&, const CostProgram& prog, const ChainDev&, const SgpmpToggles& tg) {
+    StepPlan p = {};
+    p.shape = sh; p.max_iters = p.iters = 1; p.kernel = "";
+    if (!env1("STUB_FUSED") || w.eps || sh.dtype != SGPMP_F32 || tg.no_fused_step || sh.T % 16 != 0 || sh.S % 8 != 0 || sh.P < 1) return p;
+    p.family = STEP_CHAIN; p.kernel = "stub_fused";
+    p.partials = prog.needs_fk && !tg.no_dense_partials && (sh.T * 2 * sh.n) % 4 == 0;
+    const bool nostore = w.no_samples && prog.n_ee == 0 && update_regen_rows(sh.dtype, sh.n, sh.T, sh.S, 1) > 0;
+    p.update_in_launch = nostore && env1("STUB_TAIL") && w.update_in_launch_ok;
+    p.regen_recipe = nostore && !p.update_in_launch ? 1 : 0;
+    if (p.update_in_launch && env1("STUB_PERSIST") && !tg.no_persist_planar) p.max_iters = tg.persist_max_iters >= 2 ? (int)tg.persist_max_iters : 2048;
+    if (prog.n_ee > 0) p.ee = !tg.no_ee_fold && prog.n_ee == 1 && update_ee_fold_fits(sh.dtype, sh.n, sh.T, sh.S) ? STEP_EE_FOLD : STEP_EE_LAUNCH;
+    if (w.iters > 1 && w.iters <= p.max_iters) p.iters = w.iters;
+    return p;
 }
-bool planar_seg_step(int, int, int, const PriorDev&, const CostProgram&, const ChainDev&, int, int, int, int, const SgpmpToggles&) { return false; }
-// STUB_PERSIST=1 (with STUB_FUSED, STUB_TAIL): as if the launch could run several iterations (fused_planar_seg.inc: PERSIST) --
-// sgpmp_optimize's chunking of a call is then exercised on the host; every fused launch is logged (draw, iterations) for the driver
-bool planar_persist_step(int dtype, int n, int T, const PriorDev& pr, const CostProgram& prog, const ChainDev& ch, int P, int off, int S, int ns, const SgpmpToggles& tg) {
-    return env1("STUB_PERSIST") && env1("STUB_TAIL") && !tg.no_persist_planar && fused_step_eligible(dtype, n, T, pr, prog, ch, P, off, S, ns, tg) && prog.n_ee == 0 &&
-           update_regen_rows(dtype, n, T, S, 1) > 0;
-}
+// every fused launch is logged for the driver: draw, iterations, particle range
 static unsigned long long g_log_draw[4096];
-static int g_log_iters[4096], g_log_n = 0;
+static int g_log_iters[4096], g_log_first[4096], g_log_P[4096], g_log_n = 0;
 extern "C" int stub_launch_log(int i, unsigned long long* draw, int* iters) {     // entry i of the log; returns the number of entries
     if (i >= 0 && i < g_log_n) { *draw = g_log_draw[i]; *iters = g_log_iters[i]; }
     return g_log_n;
 }
+extern "C" void stub_launch_log_range(int i, int* first, int* P) { *first = g_log_first[i]; *P = g_log_P[i]; }
 extern "C" void stub_launch_log_clear() { g_log_n = 0; }
-bool planar_tail_step(int, int, int, const PriorDev&, const CostProgram&, const ChainDev&, int, int, int, int, const SgpmpToggles&) { return false; }
-bool fused_step_eligible(int dtype, int, int T, const PriorDev&, const CostProgram&, const ChainDev&, int P, int, int S, int, const SgpmpToggles& tg) {
-    return env1("STUB_FUSED") && dtype == SGPMP_F32 && !tg.no_fused_step && T % 16 == 0 && S % 8 == 0 && P > 0;
-}
-hipError_t launch_fused_step(int dtype, int n, int T, const PriorDev& pr, const CostProgram& prog, const ChainDev& ch, uint64_t, uint64_t draw, const void* means,
-                             int P, int off, int S, void* samples, const void* spheres, int ns, const void* isw, double* zero_stats, void* costs,
-                             double* c64, hipStream_t, const SgpmpToggles& tg, const char** picked, bool* launched, const FusedDenseHost* dense,
-                             bool* armed, RegenHost* regen, bool* tail_ran) {
-    *launched = fused_step_eligible(dtype, n, T, pr, prog, ch, P, off, S, ns, tg) && samples && isw;
-    if (armed) *armed = false;
-    if (tail_ran) *tail_ran = false;
-    if (regen) std::memset(regen, 0, sizeof(*regen));
-    if (!*launched) return hipSuccess;
+hipError_t launch_fused_step(const StepPlan& plan, const StepIo& io) {
+    if (plan.family == STEP_NONE || !io.samples || !io.isw || (plan.iters > 1 && !plan.update_in_launch)) return hipErrorInvalidValue;
+    const int n = plan.shape.n, T = plan.shape.T, S = plan.shape.S, P = plan.shape.P;
     const size_t M = (size_t)T * 2 * n;
-    rd(means, (size_t)P * M * 4); rd(isw, (size_t)P * (T + 1) * 2 * n * 4); rd(spheres, (size_t)ns * 16);
-    const bool nostore = dense && dense->nostore && dense->nnz && regen && prog.n_ee == 0 && update_regen_rows(dtype, n, T, S, 1) > 0;
-    if (nostore) { regen->recipe = 1; regen->coef = pr.iso32p; regen->store_threshold = dense->store_threshold; regen->mode_offset = off; }
-    else wr(samples, (size_t)P * S * M * 4);
-    wr(costs, (size_t)P * S * 4); wr(c64, (size_t)P * S * 8); wr(zero_stats, sizeof(double) * SGPMP_STAT_SHARDS * 4);
-    if (dense && dense->nnz) rd(dense->nnz, (size_t)P * 4);
-    if (dense && dense->part && dense->nnz) {
-        wr(dense->part, (size_t)P * ((S + 7) / 8) * (M + 4) * 4);
-        if (armed) *armed = true;
+    const FusedDenseHost& d = io.dense;
+    rd(io.means, (size_t)P * M * 4); rd(io.isw, (size_t)P * (T + 1) * 2 * n * 4); rd(io.spheres, (size_t)plan.shape.n_spheres * 16);
+    if (plan.regen_recipe) rd(io.prior->iso32p, sizeof(float) * T * 8);
+    else if (!plan.update_in_launch) wr(io.samples, (size_t)P * S * M * 4);
+    wr(io.costs, (size_t)P * S * 4); wr(io.costs64, (size_t)P * S * 8); wr(io.zero_stats, sizeof(double) * SGPMP_STAT_SHARDS * 4);
+    rd(d.nnz, (size_t)P * 4);
+    if (plan.partials) wr(d.part, (size_t)P * ((S + 7) / 8) * (M + 4) * 4);
+    if (plan.update_in_launch) {                               // touches what update_kernel would
+        rd(d.tail_done, 4); wr(d.tail_done, 4); rd(d.tail_acc, sizeof(double) * SGPMP_STAT_SHARDS * 4);
+        wr(d.stats_out, sizeof(double) * SGPMP_STAT_SHARDS * 4);
+        wr(const_cast<void*>(io.means), (size_t)P * M * 4); wr(d.weights, (size_t)P * S * 4); wr(d.grad, (size_t)P * M * 4);
+        wr(d.means_prev, (size_t)P * M * 4); wr(const_cast<void*>(io.isw), (size_t)P * (T + 1) * 2 * n * 4); wr(d.nnz, (size_t)P * 4, 1);
     }
-    // STUB_TAIL=1: as if the launch updated its particles itself (fused_planar_seg.inc: seg_update) -- touches what update_kernel would
-    if (env1("STUB_TAIL") && nostore && dense->tail_done && tail_ran) {
-        regen->recipe = 0;
-        rd(dense->tail_done, 4); wr(dense->tail_done, 4); rd(dense->tail_acc, sizeof(double) * SGPMP_STAT_SHARDS * 4);
-        wr(dense->stats_out, sizeof(double) * SGPMP_STAT_SHARDS * 4);
-        wr(const_cast<void*>(means), (size_t)P * M * 4); wr(dense->weights, (size_t)P * S * 4); wr(dense->grad, (size_t)P * M * 4);
-        wr(dense->means_prev, (size_t)P * M * 4); wr(const_cast<void*>(isw), (size_t)P * (T + 1) * 2 * n * 4); wr(dense->nnz, (size_t)P * 4, 1);
-        *tail_ran = true;
-    }
-    if (dense && dense->tail_iters > 1 && !(tail_ran && *tail_ran)) return hipErrorInvalidValue;   // (as the real launcher: the caller asks planar_persist_step first)
-    if (g_log_n < 4096) { g_log_draw[g_log_n] = draw; g_log_iters[g_log_n] = (dense && dense->tail_iters > 1) ? dense->tail_iters : 1; ++g_log_n; }
-    if (picked) *picked = "stub_fused";
+    if (g_log_n < 4096) { g_log_draw[g_log_n] = io.draw; g_log_iters[g_log_n] = plan.iters; g_log_first[g_log_n] = plan.shape.offset; g_log_P[g_log_n] = P; ++g_log_n; }
     return hipSuccess;
 }
 hipError_t launch_is_weights(int dtype, int n, int T, const PriorDev& p, const void* means, int P, double, void* out, double* zero_stats, hipStream_t) {
@@ -191,8 +181,8 @@ hipError_t launch_field_eval(int dtype, const CostTerm&, const void* frames, lon
 }
 // run-time chain kernels: none in this harness (chain_rtc.hip needs hipModule*; its compile path has its own CPU test)
 const char* rtc_chain_get(const char*, int, RtcChain**) { return "no run-time compiler in the sanitizer harness"; }
-hipFunction_t rtc_kernel(RtcChain*, int, bool) { return nullptr; }
-hipError_t rtc_launch(hipFunction_t, unsigned, hipStream_t, void**, hipEvent_t) { return hipErrorNotSupported; }
+hipFunction_t rtc_kernel(RtcChain*, int, bool, bool, bool) { return nullptr; }
+hipError_t rtc_launch(hipFunction_t, unsigned, unsigned, hipStream_t, void**, hipEvent_t) { return hipErrorNotSupported; }
 const char* rtc_verify(RtcChain*, const ChainDev&, int, int* mismatch) { if (mismatch) *mismatch = 0; return "no run-time compiler in the sanitizer harness"; }
 const char* rtc_error(const RtcChain*) { return ""; }
 void rtc_stats(const RtcChain*, double* s, int* c, int* f) { if (s) *s = 0.; if (c) *c = 0; if (f) *f = 0; }

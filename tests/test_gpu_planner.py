@@ -1983,6 +1983,36 @@ def test_pipelined_optimize_equals_single_steps_bitwise(golden, kind):
     same()
 
 
+@pytest.mark.parametrize("nppg,split", [(256, True), (255, False)])
+def test_optimize_inside_the_callers_own_bracket_runs_every_iteration(golden, nppg, split):
+    """sgpmp_optimize(K = 6, SGPMP_OPT_STORE_FREE) WITHOUT SGPMP_OPT_PIPELINE between the caller's own sgpmp_pipeline_begin and
+    _end, planar fp32, n = 2, T = 16, S = 64, two goals: with 2 x 256 particles both the two-chain rule (a half brings 256
+    workgroups) and the launch of several iterations apply, and they exclude each other -- the call once planned five
+    iterations for ONE launch, the step split into two chains and ran one (advisor finding, round 6).  The means must be those
+    of six sgpmp_step calls on the same draws from the same start, bit for bit, and the store-free steps plus the storing last
+    one account for all six.  2 x 255 particles: the halves no longer qualify, one launch runs the five."""
+    goals = [[9., 6., 0., 0.], [9., -3., 0., 0.]]
+    om = planar_map(golden, F32)
+    a = hip_planar_planner(SC.PLANAR, 16, goals, nppg, 64, om, F32, seed=43, pipeline_steps=False)
+    b = hip_planar_planner(SC.PLANAR, 16, goals, nppg, 64, om, F32, seed=43, pipeline_steps=False, c_loop=False)
+    assert a.c_loop and a.store_free and torch.equal(a.particle_means, b.particle_means) and a._draw == b._draw
+    a._engine.pipeline_begin()
+    try:
+        ra = a.optimize(opt_iters=6)
+    finally:
+        a._engine.pipeline_end()
+    for _ in range(6):
+        rb = b.optimize(opt_iters=1)
+    torch.cuda.synchronize()
+    assert a._engine.last_cost_kernel() == "fused_planar_seg_kernel"
+    assert torch.equal(a.particle_means, b.particle_means)
+    for x, y in zip(ra, rb):
+        assert torch.equal(x, y)
+    assert a._engine.store_free_steps() + 1 == 6
+    assert a._engine.pipeline_split_steps() == (6 if split else 0)
+    assert a._engine.multi_iteration_launches() == (0 if split else 1)
+
+
 @pytest.mark.parametrize("dtype", ["f32", "f64"])
 def test_end_effector_goal_term_inside_the_update_kernel_bitwise(dtype):
     """CostGoal (the reference's Panda example has it, panda_environment.py:90-96): inside sgpmp_step update_kernel evaluates the

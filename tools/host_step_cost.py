@@ -18,6 +18,8 @@ else:
 for _ in range(100):
     pl.optimize(opt_iters=1, **obs)
 torch.cuda.synchronize()
+pl.step(**obs)                                       # (optimize() is one library call since round 6: a step of its own binds the call)
+torch.cuda.synchronize()
 call = next(iter(pl._step_calls.values()))
 N = 3000
 t0 = time.perf_counter()
