@@ -107,6 +107,14 @@ def plan(opt_iters, seed, num_particles_per_goal, num_samples, num_obst, traj_le
             else:
                 print(f"goal {g}: best valid particle {p}, cost {float(best.cost[g]):.4f}, "
                       f"clearance {float(best.validity.clearance[p]):.4f} m")
+                # where is the arm pushed hardest?  the continuous-time collision / limit cost of that particle and its analytic
+                # gradient with respect to the support states (one launch; no reference counterpart)
+                x = planner.particle_means[p:p + 1].clone().requires_grad_()
+                J = planner.continuous_cost(x, n_sub=4, q_limits=PANDA_Q_LIMITS, v_limits=PANDA_V_LIMITS, sigma_limit=0.1, **obs)
+                J.sum().backward()
+                rows = x.grad[0].norm(dim=-1)
+                print(f"goal {g}: continuous-time cost {float(J[0]):.4f}, largest gradient row at waypoint {int(rows.argmax())} "
+                      f"(|g| = {float(rows.max()):.4g})")
     return planner, costs
 
 

@@ -505,6 +505,41 @@ int sgpmp_dense_cost(sgpmp_ctx* ctx, const void* trajs, int64_t batch, int n_sub
                      void* stream);
 const char* sgpmp_last_dense_kernel(void);   /* thread-local static name of the kernel the last call launched; "" before */
 
+/* Value and gradient of the continuous-time cost with respect to the SUPPORT states, per trajectory b:
+ *   J[b]    = sgpmp_dense_cost's dense[b] (weight x the GRID / SPHERES / SELF terms on the inserted states + the limit penalty on all
+ *             fine states), and with support = 1 also weight x the SPHERES / SELF terms at the support waypoints 1 .. T-1 (the range
+ *             of CostCollision and sgpmp_field_grad);
+ *   grad[b] = d J[b] / d trajs[b], all T x 2n entries, velocities included.
+ * The fine states are hermite_state's (the bits sgpmp_interpolate writes).  Per fine state: forward kinematics that keeps the joint
+ * axes, the forces d field / d p_l on the link points (a term's interpolated points hand theirs to the two links they lie between),
+ * sgpmp_field_grad's backward recurrence d f / d q_j = z_j . (M_j - o_j x F_j), the limit penalty's derivative 2/sigma_limit^2 x
+ * the signed excess (C^1: zero where no limit is exceeded), and the transpose of the eight Hermite coefficients that formed the
+ * state onto x_i and x_{i+1} (m = 0: the identity).  The rbf sphere field and the SELF field are smooth; the sdf field (clamped or
+ * not) follows sgpmp_field_grad's rule: the gradient of the arg-max (point, sphere) pair, first maximum in point-major order,
+ * exactly zero where the clamp is active.
+ * Never a silently zero gradient: a GRID term (with n_sub > 0) or a SPHERES term of the occupancy type (n_spheres > 0, n_sub > 0 or
+ * support) is piecewise constant; with weight > 0 the call is refused, SGPMP_EINVAL.  weight = 0 (the limit part alone) is always
+ * allowed.  A trajectory with any non-finite fine state reports NaN in its value and in every element of grad[b], also under
+ * accumulate.  accumulate = 0 writes grad, 1 adds to what it holds; the values are always written.  Every element of grad is written
+ * once, by one lane, without atomics: two calls on the same inputs return the same bits.
+ * Link points, forces and joint axes live in one LDS column per lane: the forces of the L links in double in either dtype (their
+ * sums cancel), points and axes in the ctx dtype, L x 3 x 64 x 8 + (2 L - 1) x 3 x 64 x sizeof(real) bytes whatever the number of
+ * interpolated points (Panda: 32 KB fp32, 48 KB fp64); a chain that needs more than 64 KB is refused, SGPMP_EINVAL, with
+ * the computed bound in the message.  sgpmp_last_dense_kernel names the kernel: "dense_cost_grad_kernel<f32, 10 joints>" (chain
+ * lengths 10 and 7 with n_dof 7 and no interpolated points are compiled in), "... generic>", "... no FK>".
+ * SGPMP_EINVAL: sgpmp_dense_cost's argument errors, and a null grad with batch > 0; SGPMP_ESTATE as sgpmp_dense_cost.  batch = 0 is
+ * a no-op. */
+int sgpmp_dense_cost_grad(sgpmp_ctx* ctx, const void* trajs, int64_t batch, int n_sub, double dt,
+                          const void* spheres, int n_spheres,          /* DEVICE [n,4] or NULL */
+                          double weight,                               /* scales the collision part */
+                          const double* q_lo, const double* q_hi,      /* HOST [n_dof] or NULL */
+                          const double* v_max, double sigma_limit,     /* HOST [n_dof] or NULL; > 0 when any limit is given */
+                          int support,                                 /* 1: the collision terms also on support waypoints 1 .. T-1 */
+                          int accumulate,                              /* 0: write grad, 1: add to what grad holds */
+                          void* grad,                                  /* [B,T,d] ctx dtype, required when batch > 0 */
+                          void* costs, double* costs64,                /* [B] value, either or both may be NULL */
+                          void* stream);
+
 /* ---- GPMP: the reference's Gauss-Newton planner (planner.py:352-661) ------- */
 /* First half of GPMP._step (planner.py:580-581, cost.get_linear_system): evaluates every smooth link
  * field of the cost list and its Jacobian at waypoints 1..T-1 of the particle means [P,T,d] (kept in

@@ -106,6 +106,7 @@ SIGNATURES = {
     "sgpmp_validate": (_I, [_P, _P, _I64, _I, _D, _P, _I, _I, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), _P, _P, _P]),
     "sgpmp_dense_cost": (_I, [_P, _P, _I64, _I, _D, _P, _I, _D, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), _D, _I, _P, _P, _P]),
     "sgpmp_last_dense_kernel": (C.c_char_p, []),
+    "sgpmp_dense_cost_grad": (_I, [_P, _P, _I64, _I, _D, _P, _I, _D, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), _D, _I, _I, _P, _P, _P, _P]),
     "sgpmp_gpmp_linearize": (_I, [_P, _P, _P, _I, _P, _P]),
     "sgpmp_gpmp_solve": (_I, [_P, _P, _P, C.c_double, C.c_double, _P, _P, _P]),
     "sgpmp_event_create": (_I, [C.POINTER(_P)]),

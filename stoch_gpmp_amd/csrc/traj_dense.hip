@@ -680,3 +680,525 @@ extern "C" int sgpmp_dense_cost(sgpmp_ctx* c, const void* trajs, int64_t batch, 
                                    accumulate, costs, costs64, (hipStream_t)stream);
     return e == hipSuccess ? SGPMP_OK : dense_hip_error("sgpmp_dense_cost", e);
 }
+
+// ---------------------------------------------------------------------------------- sgpmp_dense_cost_grad
+// Value and gradient, with respect to the SUPPORT states, of sgpmp_dense_cost's sum (optionally with the SPHERES / SELF terms on
+// the support waypoints 1 .. T-1 as well).  dense_cost_kernel's mapping and the same hermite_state; per fine state the lane runs
+//   1. forward kinematics that keeps, per joint, the axis z_j (third column of the link's rotation -- the rotation about z that
+//      follows leaves it unchanged); the joint origin o_j is the link position P[j + 1] itself, so field_grad_kernel's separate
+//      origin array is not needed;
+//   2. the forces g_l = sum over terms K_term d field / d p_l on the LINK points: a term's interpolated points are never stored,
+//      each is formed from its two links when it is read and hands its force back to them (1 - alpha, alpha);
+//   3. field_grad_kernel's backward recurrence from the end effector, d f / d q_j = z_j . (M_j - o_j x F_j), F and M in double;
+//   4. the adjoint of hermite_state: (g_q, g_v) of the state times the eight coefficients that formed it, into `ga` (own row i)
+//      and `gb` (row i + 1).  Row i of the result is ga(lane i) + gb(lane i - 1): one __shfl_up per pass, lane 63's gb carried
+//      to lane 0 of the next pass in a register.  Lane i stores row i: every element is written once, by one lane, no atomics.
+// Where the points, forces and axes live: one LDS column per lane (SoA, stride 64, as MODE 1 of dense_cost_kernel) -- G of the L
+// links in double, P of the L links and Z of the L - 1 joints in the compute type.  Independent of the number of interpolated
+// points, so the Panda (L = 11) takes 32 KB in fp32 and 48 KB in fp64 whatever num_interpolate is; a chain beyond the 64 KB a workgroup may
+// ask for is refused by the host.  Registers were the first choice and do not hold them: next to the lane's six state / adjoint
+// rows of 2N reals (a, b, x, ga, gb, carry) and g_q, g_v, q, dq the 96 reals of a 10-joint chain pushed the fp32 instantiation
+// past the 512 registers of a one-wave workgroup (880 bytes of scratch per lane; fp64 1.3 KB), and scratch is slower than LDS.
+//   NJ > 0   chain length known at compile time (10: the Panda, 7), no interpolated points: the loops over links and pairs
+//            unroll, every LDS address is an immediate offset;
+//   NJ = 0   any chain, any term;
+//   NJ = -1  no link field (limits only): no LDS.
+// A non-finite fine state turns the trajectory's value and its whole gradient into NaN.  With T <= 64 the wave knows before its
+// one store; with more passes a first sweep over the fine states (hermite_state alone, no kinematics) finds out beforehand, so
+// that rows stored by an early pass never have to be written a second time.
+#define SGPMP_GRAD_LDS_MAX (64 * 1024)
+
+// this lane's columns, stride 64: G [L][3] in DOUBLE (gcol), then P [L][3] | Z [L - 1][3] in the compute type (col).  NJ > 0:
+// L = NJ + 1 at compile time, no interpolated points.  The forces are summed in double in fp32 kernels too: the pair forces of
+// the self field are equal and opposite, up to ~1e5 each with points a few centimetres apart, and what is left of them in a
+// link's sum is the gradient -- in fp32 sums the rounding of the large partial sums (~1e-2) was more than a small true gradient.
+template <typename real, int NJ>
+struct GradCols {
+    static constexpr bool FIXED = NJ > 0;
+    static constexpr int UNROLL = (NJ > 0 && sizeof(real) == 4) ? 64 : 1;   // (fp64, unrolled: 116 bytes of scratch at NJ = 10)
+    double* gcol;
+    real* col;
+    int L;
+    __device__ __forceinline__ int links() const { return FIXED ? NJ + 1 : L; }
+    __device__ __forceinline__ real p(int l, int r) const { return col[(l * 3 + r) * 64]; }
+    __device__ __forceinline__ double g(int l, int r) const { return gcol[(l * 3 + r) * 64]; }
+    __device__ __forceinline__ real z(int j, int r) const { return col[((links() + j) * 3 + r) * 64]; }
+    __device__ __forceinline__ void set_p(int l, int r, real v) { col[(l * 3 + r) * 64] = v; }
+    __device__ __forceinline__ void set_g(int l, int r, double v) { gcol[(l * 3 + r) * 64] = v; }
+    __device__ __forceinline__ void set_z(int j, int r, real v) { col[((links() + j) * 3 + r) * 64] = v; }
+};
+// bytes of dynamic LDS of a chain of L links
+template <typename real>
+static size_t grad_lds_bytes(int L) { return (size_t)L * 3 * 64 * sizeof(double) + (size_t)(2 * L - 1) * 3 * 64 * sizeof(real); }
+
+// fk_points_const's operations in the same order, keeping each joint's axis; the forces are cleared on the way
+template <typename real, int N, class S>
+__device__ __forceinline__ void fk_points_axes(ChainC chain, const real (&q)[N], S& s) {
+    using O = RealOps<real>;
+    real R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    real p[3] = {0, 0, 0};
+    const int nj = s.links() - 1;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { s.set_p(0, r, 0); s.set_g(0, r, 0); }
+#pragma unroll S::UNROLL
+    for (int j = 0; j < nj; ++j) {
+        ChainC ch = opaque(chain);                             // this joint's constants: loaded here, not hoisted and spilled
+        real F[9], tt[3];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) F[i] = JointK<real>::R(ch, j, i);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) tt[i] = JointK<real>::t(ch, j, i);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) p[r] += R[r * 3 + 0] * tt[0] + R[r * 3 + 1] * tt[1] + R[r * 3 + 2] * tt[2];
+        real Rn[9];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                Rn[r * 3 + c] = R[r * 3 + 0] * F[c] + R[r * 3 + 1] * F[3 + c] + R[r * 3 + 2] * F[6 + c];
+        if (ch->j[j].revolute) {
+            const int qidx = ch->j[j].qidx;
+            real qv = 0;
+#pragma unroll
+            for (int i = 0; i < N; ++i) qv = (qidx == i) ? q[i] : qv;
+            real sn, cs;
+            O::sincos_(qv, &sn, &cs);
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const real a = Rn[r * 3 + 0], b = Rn[r * 3 + 1];
+                Rn[r * 3 + 0] = a * cs + b * sn;
+                Rn[r * 3 + 1] = b * cs - a * sn;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R[i] = Rn[i];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            s.set_p(j + 1, r, p[r]);
+            s.set_g(j + 1, r, 0);
+            s.set_z(j, r, Rn[r * 3 + 2]);
+        }
+    }
+}
+
+// Point `idx` of a term: a link, or (idx >= L) the interpolated point `ai` between links li and li + 1 (add_interp_points' formula)
+template <typename real, class S>
+__device__ __forceinline__ void grad_point(const S& s, const TermK<real>& tm, int idx, int li, int ai, real (&p)[3]) {
+    if (S::FIXED || idx < s.links()) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r) p[r] = s.p(idx, r);
+    } else {
+        const real al = tm.alpha[ai];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const real a = s.p(li, r), b = s.p(li + 1, r);
+            p[r] = a + (b - a) * al;
+        }
+    }
+}
+// The same point in double, from the stored link points: where the forces that grad_force folds back (1 - alpha, alpha) act
+template <typename real, class S>
+__device__ __forceinline__ void grad_point_exact(const S& s, const TermK<real>& tm, int idx, int li, int ai, double (&p)[3]) {
+    if (S::FIXED || idx < s.links()) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r) p[r] = (double)s.p(idx, r);
+    } else {
+        const double al = (double)tm.alpha[ai];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const double a = (double)s.p(li, r), b = (double)s.p(li + 1, r);
+            p[r] = a + (b - a) * al;
+        }
+    }
+}
+template <typename real, typename gtype, class S>
+__device__ __forceinline__ void grad_force(S& s, const TermK<real>& tm, int idx, int li, int ai, const gtype (&g)[3]) {
+    if (S::FIXED || idx < s.links()) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r) s.set_g(idx, r, s.g(idx, r) + (double)g[r]);
+    } else {
+        const double al = (double)tm.alpha[ai];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            s.set_g(li, r, s.g(li, r) + (1.0 - al) * (double)g[r]);
+            s.set_g(li + 1, r, s.g(li + 1, r) + al * (double)g[r]);
+        }
+    }
+}
+// the points of a term in order: links 0 .. L-1, then per link interval its interpolated points
+#define GRAD_POINT_NEXT(S_, tm_, idx_, li_, ai_) \
+    if (!S_::FIXED && (idx_) >= s.links()) { if (++(ai_) == (tm_).n_interp) { (ai_) = 0; ++(li_); } }
+
+// K x (field value) of one SPHERES (rbf, sdf, clamped sdf) or SELF term; K x d field / d p_l is added to the forces
+template <typename real, class S>
+__device__ __forceinline__ real field_forces(S& s, const TermK<real>& tm, const SGPMP_CONST real* sph, int n_sph) {
+    using O = RealOps<real>;
+    const int np = S::FIXED ? s.links() : tm.n_points;
+    const real K = tm.K;
+    real val = 0;
+    if (tm.kind == SGPMP_COST_SPHERES && (tm.flags & 15) == SGPMP_FIELD_SDF) {
+        // field_grad_kernel's rule: the first maximum in point-major order, zero force where the clamp is active
+        const bool clampv = (tm.flags & SGPMP_FLAG_SDF_CLAMP) != 0;
+        real best = -std::numeric_limits<real>::infinity();
+        int bl = 0;
+        real bg[3] = {0, 0, 0};
+#pragma unroll S::UNROLL
+        for (int idx = 0, li = tm.interp_lo, ai = 0; idx < np; ++idx) {
+            real p[3];
+            grad_point<real, S>(s, tm, idx, li, ai, p);
+            for (int o = 0; o < n_sph; ++o) {
+                const real dx = p[0] - sph[o * 4], dy = p[1] - sph[o * 4 + 1], dz = p[2] - sph[o * 4 + 2];
+                const real dist = O::sqrt_(dx * dx + dy * dy + dz * dz);
+                real sd = sph[o * 4 + 3] - dist;
+                const bool cut = clampv && sd > (real)0;
+                if (cut) sd = 0;
+                if (sd > best) {
+                    best = sd; bl = idx;
+                    const real w = cut ? (real)0 : -K / dist;
+                    bg[0] = w * dx; bg[1] = w * dy; bg[2] = w * dz;
+                }
+            }
+            GRAD_POINT_NEXT(S, tm, idx, li, ai)
+        }
+        val = best;
+#pragma unroll S::UNROLL
+        for (int idx = 0, li = tm.interp_lo, ai = 0; idx < np; ++idx) {     // (uniform walk: no lane-dependent index)
+            if (idx == bl) grad_force<real>(s, tm, idx, li, ai, bg);
+            GRAD_POINT_NEXT(S, tm, idx, li, ai)
+        }
+    } else if (tm.kind == SGPMP_COST_SPHERES) {                // rbf (the occupancy count is refused by the host)
+#pragma unroll S::UNROLL
+        for (int idx = 0, li = tm.interp_lo, ai = 0; idx < np; ++idx) {
+            real p[3], g[3] = {0, 0, 0};
+            grad_point<real, S>(s, tm, idx, li, ai, p);
+            for (int o = 0; o < n_sph; ++o) {
+                const real dx = p[0] - sph[o * 4], dy = p[1] - sph[o * 4 + 1], dz = p[2] - sph[o * 4 + 2], rr = sph[o * 4 + 3];
+                const real ir2 = (real)1 / (rr * rr);
+                const real e = O::exp_((real)-0.5 * (dx * dx + dy * dy + dz * dz) * ir2);
+                val += e;
+                const real w = -e * ir2;
+                g[0] += w * dx; g[1] += w * dy; g[2] += w * dz;
+            }
+#pragma unroll
+            for (int r = 0; r < 3; ++r) g[r] *= K;
+            grad_force<real>(s, tm, idx, li, ai, g);
+            GRAD_POINT_NEXT(S, tm, idx, li, ai)
+        }
+    } else {                                                   // SELF: diagonal (1 each, no force) + twice the strict lower triangle
+        val = (real)np;
+        const real k4 = (real)4 * tm.K2 * K;
+#pragma unroll S::UNROLL
+        for (int i = 1, il = tm.interp_lo, ia = 0; i < np; ++i) {
+            real pi[3];
+            double pid[3], gi[3] = {0, 0, 0};
+            grad_point<real, S>(s, tm, i, il, ia, pi);
+            grad_point_exact<real, S>(s, tm, i, il, ia, pid);
+#pragma unroll S::UNROLL
+            for (int j = 0, jl = tm.interp_lo, ja = 0; j < i; ++j) {
+                real pj[3];
+                double pjd[3];
+                grad_point<real, S>(s, tm, j, jl, ja, pj);
+                grad_point_exact<real, S>(s, tm, j, jl, ja, pjd);
+                const real dx = pi[0] - pj[0], dy = pi[1] - pj[1], dz = pi[2] - pj[2];
+                const real e = O::exp_((dx * dx + dy * dy + dz * dz) * tm.K2);
+                val += (real)2 * e;
+                const real w = k4 * e;
+                // the force along the difference of the two points IN DOUBLE, where the folded forces act: the pair's moment
+                // (p_i - p_j) x g is then zero to double rounding, as it is in exact arithmetic, instead of |g| |p_i - p_j| 2^-24
+                const double wd = (double)w;
+                const double fx = wd * (pid[0] - pjd[0]), fy = wd * (pid[1] - pjd[1]), fz = wd * (pid[2] - pjd[2]);
+                const double gj[3] = {-fx, -fy, -fz};
+                gi[0] += fx; gi[1] += fy; gi[2] += fz;
+                grad_force<real>(s, tm, j, jl, ja, gj);
+                GRAD_POINT_NEXT(S, tm, j, jl, ja)
+            }
+            grad_force<real>(s, tm, i, il, ia, gi);
+            GRAD_POINT_NEXT(S, tm, i, il, ia)
+        }
+    }
+    return K * val;
+}
+
+// field_grad_kernel's backward recurrence from the end effector: dq[k] = sum over the revolute joints j of q_k of z_j . (M_j - o_j x F_j)
+template <typename real, int N, class S>
+__device__ __forceinline__ void joint_torques(ChainC chain, const S& s, real (&dq)[N]) {
+    double Fs[3] = {0, 0, 0}, Ms[3] = {0, 0, 0};             // (double, as the forces: GradCols)
+#pragma unroll
+    for (int k = 0; k < N; ++k) dq[k] = 0;
+    const int nj = s.links() - 1;
+#pragma unroll S::UNROLL
+    for (int j = nj - 1; j >= 0; --j) {
+        ChainC ch = opaque(chain);
+        const int l = j + 1;
+        const double px = s.p(l, 0), py = s.p(l, 1), pz = s.p(l, 2), gx = s.g(l, 0), gy = s.g(l, 1), gz = s.g(l, 2);
+        Fs[0] += gx; Fs[1] += gy; Fs[2] += gz;
+        Ms[0] += py * gz - pz * gy;
+        Ms[1] += pz * gx - px * gz;
+        Ms[2] += px * gy - py * gx;
+        if (ch->j[j].revolute) {
+            const int qidx = ch->j[j].qidx;
+            const double tx = Ms[0] - (py * Fs[2] - pz * Fs[1]);
+            const double ty = Ms[1] - (pz * Fs[0] - px * Fs[2]);
+            const double tz = Ms[2] - (px * Fs[1] - py * Fs[0]);
+            const real d = (real)((double)s.z(j, 0) * tx + (double)s.z(j, 1) * ty + (double)s.z(j, 2) * tz);
+#pragma unroll
+            for (int k = 0; k < N; ++k) dq[k] += (qidx == k) ? d : (real)0;
+        }
+    }
+}
+
+static_assert(sizeof(DenseCostK<double>) + sizeof(HermiteK<double>) + 6 * sizeof(void*) <= 4096, "dense_cost_grad_kernel: kernel arguments");
+
+template <typename real, int N, int NJ>
+__global__ void __launch_bounds__(64)
+dense_cost_grad_kernel(const real* __restrict__ trajs, long long batch, DenseCostK<real> A, HermiteK<real> H, int support,
+                       real* __restrict__ grad, real* __restrict__ costs, double* __restrict__ costs64) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const int lane = threadIdx.x;
+    const int T = A.T, k1 = A.n_sub + 1;
+    const real big = std::numeric_limits<real>::max();
+    const real two_is2 = (real)2 * A.inv_sigma2;
+    for (long long b = blockIdx.x; b < batch; b += gridDim.x) {
+        const real* tr = trajs + (size_t)b * T * (2 * N);
+        real* gr = grad + (size_t)b * T * (2 * N);
+        bool any_bad = false;
+        if (T > 64) {                                          // several passes: know about a non-finite state before the first store
+            bool bad = false;
+#pragma unroll 1
+            for (int base = 0; base < T; base += 64) {
+                const int i = base + lane;
+                real a[2 * N], nb[2 * N], x[2 * N];
+                load_interval<real, N>(tr, T, i, lane, a, nb);
+                const int nm = i < T - 1 ? k1 : (i == T - 1 ? 1 : 0);
+#pragma unroll 1
+                for (int m = 0; m < nm; ++m) {
+                    if (m == 0) {
+#pragma unroll
+                        for (int k = 0; k < 2 * N; ++k) x[k] = a[k];
+                    } else {
+                        hermite_state<real, N>(a, nb, H.c[m - 1], x);
+                    }
+#pragma unroll
+                    for (int k = 0; k < 2 * N; ++k) bad = bad || !(fabs(x[k]) <= big);
+                }
+            }
+            any_bad = __any(bad ? 1 : 0) != 0;
+        }
+        real part = 0, lim = 0;
+        real carry[2 * N];                                     // lane 63's gb of the previous pass (every lane holds it)
+#pragma unroll
+        for (int k = 0; k < 2 * N; ++k) carry[k] = 0;
+#pragma unroll 1
+        for (int base = 0; base < T; base += 64) {
+            const int i = base + lane;
+            real a[2 * N], nb[2 * N], x[2 * N], ga[2 * N], gb[2 * N];
+            load_interval<real, N>(tr, T, i, lane, a, nb);
+#pragma unroll
+            for (int k = 0; k < 2 * N; ++k) { ga[k] = 0; gb[k] = 0; }
+            const int nm = (any_bad || i >= T) ? 0 : (i < T - 1 ? k1 : 1);
+            bool bad = false;
+#pragma unroll 1
+            for (int m = 0; m < nm; ++m) {
+                if (m == 0) {
+#pragma unroll
+                    for (int k = 0; k < 2 * N; ++k) x[k] = a[k];
+                } else {
+                    hermite_state<real, N>(a, nb, H.c[m - 1], x);
+                }
+                // explicit test: fmin / fmax drop a NaN, comparisons with one are all false
+                bool finite = true;
+#pragma unroll
+                for (int k = 0; k < 2 * N; ++k) finite = finite && (fabs(x[k]) <= big);
+                if (!finite) { bad = true; continue; }
+                real gq[N], gv[N];
+#pragma unroll
+                for (int k = 0; k < N; ++k) { gq[k] = 0; gv[k] = 0; }
+                if (A.has_qlim | A.has_vlim) {                 // C^1: 2 / sigma^2 x the signed excess, zero inside the limits
+#pragma unroll
+                    for (int k = 0; k < N; ++k) {
+                        if (A.has_qlim) {
+                            const real lo = A.q_lo[k] - x[k], hi = x[k] - A.q_hi[k];
+                            if (lo > 0) { lim += lo * lo; gq[k] -= two_is2 * lo; }
+                            if (hi > 0) { lim += hi * hi; gq[k] += two_is2 * hi; }
+                        }
+                        if (A.has_vlim) {
+                            const real ve = fabs(x[N + k]) - A.v_max[k];
+                            if (ve > 0) { lim += ve * ve; gv[k] += x[N + k] < 0 ? -two_is2 * ve : two_is2 * ve; }
+                        }
+                    }
+                }
+                if constexpr (NJ >= 0) {
+                    if (m > 0 || (support && i >= 1)) {        // inserted states; with `support`, waypoints 1 .. T-1 as well
+                        real q[N], dq[N];
+#pragma unroll
+                        for (int k = 0; k < N; ++k) q[k] = x[k];
+                        const SGPMP_CONST real* sph = as_const(A.spheres);
+                        real f = 0;
+                        GradCols<real, NJ> s = {reinterpret_cast<double*>(lds_raw) + lane,
+                                                reinterpret_cast<real*>(lds_raw + (size_t)A.n_links * 3 * 64 * sizeof(double)) + lane,
+                                                A.n_links};
+                        fk_points_axes<real, N>(as_const(A.chain), q, s);
+                        for (int ti = 0; ti < A.n_terms; ++ti) f += field_forces<real>(s, A.t[ti], sph, A.n_spheres);
+                        joint_torques<real, N>(as_const(A.chain), s, dq);
+                        part += f;
+#pragma unroll
+                        for (int k = 0; k < N; ++k) gq[k] += A.weight * dq[k];
+                    }
+                }
+                if (m == 0) {                                  // the support state itself: the identity
+#pragma unroll
+                    for (int k = 0; k < N; ++k) { ga[k] += gq[k]; ga[N + k] += gv[k]; }
+                } else {                                       // the transpose of hermite_state's eight coefficients
+                    const real* c = H.c[m - 1];
+#pragma unroll
+                    for (int k = 0; k < N; ++k) {
+                        ga[k] += c[0] * gq[k] + c[4] * gv[k];
+                        ga[N + k] += c[1] * gq[k] + c[5] * gv[k];
+                        gb[k] += c[2] * gq[k] + c[6] * gv[k];
+                        gb[N + k] += c[3] * gq[k] + c[7] * gv[k];
+                    }
+                }
+            }
+            if (T <= 64) any_bad = __any(bad ? 1 : 0) != 0;    // (one pass: nothing has been stored yet)
+            const real nan = std::numeric_limits<real>::quiet_NaN();
+            real* row = gr + (size_t)(i < T ? i : 0) * (2 * N);
+#pragma unroll
+            for (int k = 0; k < 2 * N; ++k) {
+                real up = __shfl_up(gb[k], 1, 64);
+                if (lane == 0) up = carry[k];
+                carry[k] = __shfl(gb[k], 63, 64);
+                real v = ga[k] + up;
+                if (any_bad) v = nan;
+                if (i < T) row[k] = A.accumulate ? row[k] + v : v;
+            }
+        }
+        double acc = wave_sum((double)(A.weight * part) + (double)(A.inv_sigma2 * lim));
+        if (lane == 0) {
+            if (any_bad) acc = std::numeric_limits<double>::quiet_NaN();
+            if (costs64) costs64[b] = acc;
+            if (costs) costs[b] = (real)acc;
+        }
+    }
+}
+
+// SGPMP_OK, or the code of a refusal (message set)
+template <typename real>
+static int launch_dense_cost_grad(const SgpmpCtxView& v, const void* trajs, long long batch, int n_sub, double dt,
+                                  const void* spheres, int n_spheres, double weight, const double* q_lo, const double* q_hi,
+                                  const double* v_max, double sigma_limit, int support, int accumulate, void* grad, void* costs,
+                                  double* costs64, hipStream_t stream) {
+    constexpr bool f64 = sizeof(real) == 8;
+    const int n = v.dims.n_dof;
+    DenseCostK<real> A;
+    std::memset(&A, 0, sizeof(A));
+    A.T = v.dims.traj_len; A.n_sub = n_sub; A.accumulate = accumulate ? 1 : 0;
+    A.weight = (real)weight;
+    bool interp = false;
+    // weight 0 (the limit part alone) evaluates no field; neither does n_sub 0 without the support waypoints
+    for (int i = 0; v.prog && weight > 0. && (n_sub > 0 || support) && i < v.prog->n_terms; ++i) {
+        const CostTerm& s = v.prog->terms[i];
+        if (s.kind != SGPMP_COST_SPHERES && s.kind != SGPMP_COST_SELF) continue;   // (a GRID term with n_sub > 0 was refused)
+        if (s.kind == SGPMP_COST_SPHERES && n_spheres < 1) continue;               // no obstacle: the term adds nothing
+        A.t[A.n_terms++] = make_termk<real>(s);
+        interp = interp || s.n_interp > 0;
+    }
+    const real inf = std::numeric_limits<real>::infinity();
+    A.has_qlim = (q_lo || q_hi) ? 1 : 0;
+    A.has_vlim = v_max ? 1 : 0;
+    A.inv_sigma2 = (A.has_qlim | A.has_vlim) ? (real)(1. / (sigma_limit * sigma_limit)) : (real)0;
+    for (int k = 0; k < SGPMP_MAX_DOF; ++k) {                  // a one-sided position limit: the other side never binds
+        A.q_lo[k] = (q_lo && k < n) ? (real)q_lo[k] : -inf;
+        A.q_hi[k] = (q_hi && k < n) ? (real)q_hi[k] : inf;
+        A.v_max[k] = (v_max && k < n) ? (real)v_max[k] : inf;
+    }
+    const HermiteK<real> H = hermite_coefs<real>(n_sub, dt);
+    const dim3 grid(dense_blocks(batch)), block(64);
+    const char* name = "";
+    size_t lds = 0;
+    int nj = -1;                                               // -1: no link field; 0: generic; 10, 7: compile-time chain length
+    if (A.n_terms > 0) {
+        A.spheres = n_spheres > 0 ? (const real*)spheres : nullptr;
+        A.n_spheres = A.spheres ? n_spheres : 0;
+        A.n_links = v.h_chain->n_links;
+        A.chain = v.d_chain;
+        const int joints = v.h_chain->n_joints;
+        nj = (n == 7 && (joints == 10 || joints == 7) && !interp && !v.tg->force_generic_fk) ? joints : 0;
+        {
+            lds = grad_lds_bytes<real>(A.n_links);
+            if (lds > SGPMP_GRAD_LDS_MAX) {
+                char msg[256];
+                snprintf(msg, sizeof(msg), "sgpmp_dense_cost_grad: a chain of %d links needs %d x 3 x 64 x 8 (forces) + (2 x %d - 1) x 3 x 64 x %d "
+                         "(points, joint axes) = %zu bytes of LDS columns, the kernel's budget is %d: at most %d links in this dtype",
+                         A.n_links, A.n_links, A.n_links, (int)sizeof(real), lds, SGPMP_GRAD_LDS_MAX,
+                         (int)((SGPMP_GRAD_LDS_MAX / 192 + sizeof(real)) / (8 + 2 * sizeof(real))));
+                return sgpmp_set_error(SGPMP_EINVAL, msg);
+            }
+        }
+    }
+#define GRAD_LAUNCH(NN, NJ_)                                                                                          \
+    hipLaunchKernelGGL((dense_cost_grad_kernel<real, NN, NJ_>), grid, block, lds, stream, (const real*)trajs, batch, \
+                       A, H, support ? 1 : 0, (real*)grad, (real*)costs, costs64)
+#define GRAD_CASE(NN, NJ_) case NN: GRAD_LAUNCH(NN, NJ_); break;
+    if (nj == 10) {
+        name = f64 ? "dense_cost_grad_kernel<f64, 10 joints>" : "dense_cost_grad_kernel<f32, 10 joints>";
+        GRAD_LAUNCH(7, 10);
+    } else if (nj == 7) {
+        name = f64 ? "dense_cost_grad_kernel<f64, 7 joints>" : "dense_cost_grad_kernel<f32, 7 joints>";
+        GRAD_LAUNCH(7, 7);
+    } else if (nj == 0) {
+        name = f64 ? "dense_cost_grad_kernel<f64, generic>" : "dense_cost_grad_kernel<f32, generic>";
+        switch (n) {
+            GRAD_CASE(1, 0) GRAD_CASE(2, 0) GRAD_CASE(3, 0) GRAD_CASE(4, 0) GRAD_CASE(5, 0) GRAD_CASE(6, 0) GRAD_CASE(7, 0) GRAD_CASE(8, 0)
+            default: return sgpmp_set_error(SGPMP_EINVAL, "sgpmp_dense_cost_grad: n_dof out of range");
+        }
+    } else {
+        name = f64 ? "dense_cost_grad_kernel<f64, no FK>" : "dense_cost_grad_kernel<f32, no FK>";
+        switch (n) {
+            GRAD_CASE(1, -1) GRAD_CASE(2, -1) GRAD_CASE(3, -1) GRAD_CASE(4, -1) GRAD_CASE(5, -1) GRAD_CASE(6, -1) GRAD_CASE(7, -1) GRAD_CASE(8, -1)
+            default: return sgpmp_set_error(SGPMP_EINVAL, "sgpmp_dense_cost_grad: n_dof out of range");
+        }
+    }
+#undef GRAD_CASE
+#undef GRAD_LAUNCH
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return dense_hip_error("sgpmp_dense_cost_grad", e);
+    g_last_dense_kernel = name;                                // published only once the launch has been accepted
+    return SGPMP_OK;
+}
+
+extern "C" int sgpmp_dense_cost_grad(sgpmp_ctx* c, const void* trajs, int64_t batch, int n_sub, double dt, const void* spheres,
+                                     int n_spheres, double weight, const double* q_lo, const double* q_hi, const double* v_max,
+                                     double sigma_limit, int support, int accumulate, void* grad, void* costs, double* costs64,
+                                     void* stream) {
+    const bool limits = q_lo || q_hi || v_max;
+    if (!c || batch < 0 || n_sub < 0 || n_sub > SGPMP_MAX_SUBSTEPS || !(dt > 0.) || !(weight >= 0.) || n_spheres < 0 ||
+        (limits && !(sigma_limit > 0.)) || (batch > 0 && (!trajs || !grad)))
+        return sgpmp_set_error(SGPMP_EINVAL, "sgpmp_dense_cost_grad: bad argument (n_sub in [0, 31], dt > 0, weight >= 0, "
+                                             "sigma_limit > 0 with limits, non-null trajs and grad)");
+    SgpmpCtxView v;
+    const int view_rc = sgpmp_ctx_view(c, &v);
+    if (view_rc != SGPMP_OK) return view_rc;                   // (finalize_program said why)
+    for (int i = 0; v.prog && i < v.prog->n_terms; ++i) {
+        const int kind = v.prog->terms[i].kind;
+        if ((kind == SGPMP_COST_SPHERES || kind == SGPMP_COST_SELF) && !v.have_chain)
+            return sgpmp_set_error(SGPMP_ESTATE, "sgpmp_dense_cost_grad: link-field terms need an FK chain (sgpmp_set_fk)");
+        if (kind == SGPMP_COST_SPHERES && n_spheres > 0 && !spheres)
+            return sgpmp_set_error(SGPMP_ESTATE, "sgpmp_dense_cost_grad: n_spheres > 0 without obstacle spheres");
+    }
+    // never a silently zero gradient: the piecewise-constant terms are refused wherever a state would evaluate them
+    for (int i = 0; v.prog && weight > 0. && i < v.prog->n_terms; ++i) {
+        const CostTerm& s = v.prog->terms[i];
+        if (s.kind == SGPMP_COST_GRID && n_sub > 0)
+            return sgpmp_set_error(SGPMP_EINVAL, "sgpmp_dense_cost_grad: the grid lookup is piecewise constant and has no gradient "
+                                                 "(weight = 0 gives the limit part alone)");
+        if (s.kind == SGPMP_COST_SPHERES && (s.flags & 15) == SGPMP_FIELD_OCCUPANCY && n_spheres > 0 && (n_sub > 0 || support))
+            return sgpmp_set_error(SGPMP_EINVAL, "sgpmp_dense_cost_grad: the occupancy count is piecewise constant and has no gradient "
+                                                 "(rbf and sdf sphere fields do; weight = 0 gives the limit part alone)");
+    }
+    if (batch == 0) return SGPMP_OK;
+    return v.dims.dtype == SGPMP_F64
+        ? launch_dense_cost_grad<double>(v, trajs, batch, n_sub, dt, spheres, n_spheres, weight, q_lo, q_hi, v_max, sigma_limit,
+                                         support, accumulate, grad, costs, costs64, (hipStream_t)stream)
+        : launch_dense_cost_grad<float>(v, trajs, batch, n_sub, dt, spheres, n_spheres, weight, q_lo, q_hi, v_max, sigma_limit,
+                                        support, accumulate, grad, costs, costs64, (hipStream_t)stream);
+}

@@ -1,5 +1,5 @@
 """Host-side arithmetic of the dense (GP-interpolated) trajectories: index bookkeeping and the interpolation weights that
-`sgpmp_interpolate` / `sgpmp_validate` / `sgpmp_dense_cost` (csrc/traj_dense.hip) apply on the GPU.  numpy only, no GPU, no library.
+`sgpmp_interpolate` / `sgpmp_validate` / `sgpmp_dense_cost` / `sgpmp_dense_cost_grad` (csrc/traj_dense.hip) apply on the GPU.  numpy only, no GPU, no library.
 
 Between two support states x_i = (q_i, v_i) and x_{i+1}, `dt` apart, the posterior mean of the constant-velocity GP prior is
 
@@ -88,3 +88,48 @@ def limit_penalty(fine, q_limits=None, v_limits=None, sigma_limit=None):
     if v_limits is not None:
         out += (np.maximum(np.abs(v) - np.asarray(v_limits, dtype=np.float64), 0.) ** 2).sum(axis=(-2, -1))
     return out / float(sigma_limit) ** 2
+
+
+def hermite_pullback(g_fine, T, n_sub, dt):
+    """The transpose of `interpolate`: a gradient with respect to the fine states [..., T_f, 2n] -> the gradient with respect to
+    the support states [..., T, 2n], in fp64.  Fine state m of interval i hands Lambda[m]^T g to x_i and Psi[m]^T g to x_{i+1}
+    (m = 0 and the last state: the identity) -- what `sgpmp_dense_cost_grad` does per lane."""
+    g = np.asarray(g_fine, dtype=np.float64)
+    T, n_sub = int(T), int(n_sub)
+    n = g.shape[-1] // 2
+    if g.shape[-2] != fine_length(T, n_sub):
+        raise ValueError(f"hermite_pullback: {g.shape[-2]} fine states, T = {T} and n_sub = {n_sub} give {fine_length(T, n_sub)}")
+    lam, psi = hermite_weights(n_sub, dt)
+    k1 = n_sub + 1
+    out = np.zeros(g.shape[:-2] + (T, 2 * n), dtype=np.float64)
+    out[..., -1, :] = g[..., -1, :]
+    out[..., :-1, :] = g[..., 0:-1:k1, :]
+    for m in range(1, k1):
+        gq, gv = g[..., m:-1:k1, :n], g[..., m:-1:k1, n:]
+        la, ps = lam[m], psi[m]
+        out[..., :-1, :n] += la[0, 0] * gq + la[1, 0] * gv
+        out[..., :-1, n:] += la[0, 1] * gq + la[1, 1] * gv
+        out[..., 1:, :n] += ps[0, 0] * gq + ps[1, 0] * gv
+        out[..., 1:, n:] += ps[0, 1] * gq + ps[1, 1] * gv
+    return out
+
+
+def limit_penalty_grad(fine, q_limits=None, v_limits=None, sigma_limit=None):
+    """d `limit_penalty` / d fine states, [..., T_f, 2n] in fp64: 2/sigma_limit^2 x the signed excess, zero where no limit is
+    exceeded (the penalty is C^1).  A limit that is not given contributes nothing."""
+    x = np.asarray(fine, dtype=np.float64)
+    n = x.shape[-1] // 2
+    q, v = x[..., :n], x[..., n:]
+    out = np.zeros(x.shape, dtype=np.float64)
+    q_lo, q_hi = (None, None) if q_limits is None else q_limits
+    if q_lo is None and q_hi is None and v_limits is None:
+        return out
+    if sigma_limit is None or not float(sigma_limit) > 0.:
+        raise ValueError("limit_penalty_grad: limits need sigma_limit > 0")
+    if q_lo is not None:
+        out[..., :n] -= np.maximum(np.asarray(q_lo, dtype=np.float64) - q, 0.)
+    if q_hi is not None:
+        out[..., :n] += np.maximum(q - np.asarray(q_hi, dtype=np.float64), 0.)
+    if v_limits is not None:
+        out[..., n:] += np.sign(v) * np.maximum(np.abs(v) - np.asarray(v_limits, dtype=np.float64), 0.)
+    return out * (2. / float(sigma_limit) ** 2)

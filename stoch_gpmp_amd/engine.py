@@ -626,8 +626,37 @@ class Engine:
                                               1 if accumulate else 0, L.ptr(out), L.ptr(out64), L.stream_ptr()))
         return out if out is not None else out64
 
+    def dense_cost_grad(self, trajs, n_sub, dt, spheres=None, weight=1.0, q_limits=None, v_limits=None, sigma_limit=None,
+                        support=False, grad=None, accumulate=False):
+        """Value [B] (float64) and gradient [B,T,d] (ctx dtype), with respect to the support states, of dense_cost()'s sum; with
+        `support` the SPHERES / SELF terms also count at the support waypoints 1 .. T-1 (include/sgpmp.h: sgpmp_dense_cost_grad;
+        numpy twins of the pieces: dense.hermite_pullback, dense.limit_penalty_grad).  accumulate: add to what `grad` holds.
+        A GRID or occupancy term that a state would evaluate with weight > 0 has no gradient: ValueError."""
+        self._chk(trajs, "trajs")
+        B = trajs.numel() // (self.T * self.d)
+        if grad is None:
+            if accumulate:
+                raise ValueError("dense_cost_grad: accumulate needs the tensor to add to (grad)")
+            grad = torch.empty(B, self.T, self.d, **self.tensor_args)
+        self._chk(grad, "grad")
+        if grad.numel() != B * self.T * self.d:
+            raise ValueError(f"dense_cost_grad: grad holds {grad.numel()} numbers, the batch needs {B * self.T * self.d}")
+        n_sph = 0
+        if spheres is not None:
+            spheres = spheres.reshape(-1, 4)
+            self._chk(spheres, "obstacle_spheres")
+            n_sph = spheres.shape[0]
+        q_lo, q_hi, v_max = self._host_limits(q_limits, v_limits)
+        value = torch.empty(B, device=self.device, dtype=torch.float64)
+        with torch.cuda.device(self.device):
+            L.check(self.lib.sgpmp_dense_cost_grad(self._ctx, L.ptr(trajs), B, int(n_sub), float(dt), L.ptr(spheres), n_sph,
+                                                   float(weight), q_lo, q_hi, v_max,
+                                                   0.0 if sigma_limit is None else float(sigma_limit), 1 if support else 0,
+                                                   1 if accumulate else 0, L.ptr(grad), None, L.ptr(value), L.stream_ptr()))
+        return value, grad
+
     def last_dense_kernel(self):
-        """Name of the kernel this thread's last dense_cost() launched ("" before the first)."""
+        """Name of the kernel this thread's last dense_cost() / dense_cost_grad() launched ("" before the first)."""
         return self.lib.sgpmp_last_dense_kernel().decode()
 
     # ------------------------------------------------------------------ GPMP (Gauss-Newton planner)

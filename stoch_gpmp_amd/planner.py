@@ -66,6 +66,25 @@ from .engine import Engine
 _UNSEEDED = itertools.count()
 
 
+
+class _ContinuousCost(torch.autograd.Function):
+    """Engine.dense_cost_grad as a differentiable op: forward keeps the gradient the launch computed with the value, backward
+    scales trajectory b's rows by the upstream weight of value b."""
+
+    @staticmethod
+    def forward(ctx, trajs, engine, n_sub, dt, spheres, weight, q_limits, v_limits, sigma_limit, support):
+        value, grad = engine.dense_cost_grad(trajs.detach(), n_sub, dt, spheres=spheres, weight=weight, q_limits=q_limits,
+                                             v_limits=v_limits, sigma_limit=sigma_limit, support=support)
+        ctx.save_for_backward(grad)
+        return value
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        grad, = ctx.saved_tensors
+        return (grad_out.to(grad.dtype)[:, None, None] * grad,) + (None,) * 9
+
+
 class TrajectoryValidity:
     """Result of StochGPMP.validate_trajectories: per trajectory, over all fine states of its GP interpolation,
     `clearance` (min link-to-sphere distance), `self_clearance` (min distance of the link pairs that move against each other),
@@ -825,6 +844,31 @@ class StochGPMP:
         values, where = self._engine.validate(self._dense_input(trajs), n_sub, self.dt, spheres=spheres,
                                               grid_term=self._grid_term(), q_limits=q_limits, v_limits=v_limits)
         return TrajectoryValidity(values, where, n_sub, buffer, self_buffer)
+
+    def continuous_cost(self, trajs=None, n_sub=None, weight=None, q_limits=None, v_limits=None, sigma_limit=None, support=True,
+                        **observation):
+        """The continuous-time collision and limit cost of trajs [B,T,d] (default: this rank's particle means) as a [B] tensor
+        that torch can differentiate: weight x the sphere / self terms of the cost program on the n_sub GP-interpolated states
+        per interval (with `support` also on the support waypoints 1 .. T-1) plus the joint / velocity limit penalty on all fine
+        states, value and analytic gradient from one launch (include/sgpmp.h: sgpmp_dense_cost_grad).  Arguments left None take
+        the planner's dense_cost setting, then set_dense_cost's defaults.  Without requires_grad it is a plain evaluation; the
+        backward is once-differentiable."""
+        cfg = dict(n_sub=4, weight=1.0, q_limits=None, v_limits=None, sigma_limit=None)
+        if self._dense is not None:
+            cfg.update(self._dense)
+        for key, given in (('n_sub', n_sub), ('weight', weight), ('q_limits', q_limits), ('v_limits', v_limits),
+                           ('sigma_limit', sigma_limit)):
+            if given is not None:
+                cfg[key] = given
+        if not self._native_cost:
+            raise ValueError("continuous_cost needs a cost the library evaluates itself (a CostComposite compiled into the engine)")
+        if self._cost_version != self.cost.version():
+            self.cost.compile_into(self._engine)
+            self._cost_version = self.cost.version()
+        has_chain = getattr(self.cost, "chain", None) is not None
+        spheres = self._spheres(observation) if has_chain else None
+        return _ContinuousCost.apply(self._dense_input(trajs), self._engine, int(cfg['n_sub']), float(self.dt), spheres,
+                                     float(cfg['weight']), cfg['q_limits'], cfg['v_limits'], cfg['sigma_limit'], bool(support))
 
     def best_trajectories(self, n_sub=4, buffer=0., self_buffer=0., q_limits=None, v_limits=None, **observation):
         """Per goal, the lowest-cost particle among those that pass validate_trajectories: all particles of all ranks
