@@ -558,6 +558,29 @@ int sgpmp_gpmp_linearize(sgpmp_ctx* ctx, const void* means, const void* spheres,
 int sgpmp_gpmp_solve(sgpmp_ctx* ctx, void* means, const double* diag_sum, double delta, double step_size,
                      void* d_theta, void* costs, void* stream);
 
+/* Continuous-time factors in that linear system (no reference counterpart: the reference's GPMP has rows at the T support
+ * waypoints only).  With n_sub = k states inserted per interval by the interpolation of sgpmp_interpolate (fine state m of
+ * interval i: x_f = Lambda[m] x_i + Psi[m] x_{i+1}), sgpmp_gpmp_linearize / sgpmp_gpmp_solve add, all as scalar rows
+ * (A row = -d error / d x, b = error):
+ *   - for every SPHERES (rbf, sdf, clamped sdf) and SELF term, at every inserted state m = 1 .. k of every interval, the row
+ *     error = field_term(q_f), precision = weight x K_term, entries -(Lambda[m][0][0], Lambda[m][0][1]) g on (q_i, q'_i) and
+ *     -(Psi[m][0][0], Psi[m][0][1]) g on (q_{i+1}, q'_{i+1}), g = d field / d q_f as sgpmp_field_grad returns it.  The support
+ *     waypoints 1 .. T-1 keep their rows with K_term, an EE_GOAL term its one row on the last waypoint;
+ *   - per degree of freedom at ALL fine states the limit rows max(0, q_lo - q), max(0, q - q_hi), max(0, |q'| - v_max) with
+ *     precision 1/sigma_limit^2 (b^T K b of them is sgpmp_dense_cost's limit penalty); an inactive row is a zero row, a limit
+ *     that is not given (NULL; one side alone is allowed) contributes nothing.
+ * The normal matrix stays block-tridiagonal with a per-interval sub-diagonal block: sgpmp_gpmp_solve then runs
+ * gpmp_dense_solve_kernel (csrc/gpmp_dense.hip), `costs` counts the new rows, and `diag_sum` of sgpmp_gpmp_linearize carries
+ * their part of diag(A^T K A) -- velocity entries and waypoint 0 included.  q_lo, q_hi, v_max: HOST double[n_dof], copied.
+ * n_sub = 0 or weight = 0 with no limit given switches the option OFF: linearize and solve are then those without it, bit for
+ * bit.  A change of the setting takes effect at the next sgpmp_gpmp_linearize (a solve in between: SGPMP_ESTATE).
+ * SGPMP_EINVAL: n_sub outside [0, SGPMP_MAX_SUBSTEPS], dt <= 0, weight < 0, a limit with sigma_limit <= 0. */
+int sgpmp_gpmp_set_dense(sgpmp_ctx* ctx, int n_sub, double dt, double weight, const double* q_lo, const double* q_hi,
+                         const double* v_max, double sigma_limit);
+/* Name of the solve kernel of this thread's last sgpmp_gpmp_solve ("gpmp_thomas_kernel", "gpmp_solve_kernel",
+ * "gpmp_dense_solve_kernel"; "" before): for the tests that must prove which kernel they exercised.  Static string. */
+const char* sgpmp_last_gpmp_kernel(void);
+
 /* Kernel timing helper for bench.py: elapsed ms between two events recorded on `stream`
  * (HIP events on the stream the kernels run on). */
 int sgpmp_event_create(void** ev);

@@ -109,6 +109,8 @@ SIGNATURES = {
     "sgpmp_dense_cost_grad": (_I, [_P, _P, _I64, _I, _D, _P, _I, _D, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), _D, _I, _I, _P, _P, _P, _P]),
     "sgpmp_gpmp_linearize": (_I, [_P, _P, _P, _I, _P, _P]),
     "sgpmp_gpmp_solve": (_I, [_P, _P, _P, C.c_double, C.c_double, _P, _P, _P]),
+    "sgpmp_gpmp_set_dense": (_I, [_P, _I, _D, _D, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), _D]),
+    "sgpmp_last_gpmp_kernel": (C.c_char_p, []),
     "sgpmp_event_create": (_I, [C.POINTER(_P)]),
     "sgpmp_event_record": (_I, [_P, _P]),
     "sgpmp_event_elapsed_ms": (_I, [_P, _P, C.POINTER(C.c_float)]),

@@ -66,6 +66,10 @@ struct sgpmp_ctx {
     double* d_gscratch;           // [P][T][2][256] block factors
     double* d_diag;               // [T*d] field part of sum_p diag(A^T K A)
     int* d_gstatus;
+    // continuous-time factors of the GPMP system (sgpmp_gpmp_set_dense); on = false: linearize / solve as without the option
+    struct { bool on = false; GpmpDenseArgs k = {}; } gdense;
+    void* d_gfine = nullptr;      // [P, T_f, d] the means on the fine grid
+    size_t g_fine1 = 0;           // fine states per particle the field buffers above hold (T_f - 1; T - 1 with the option off)
     double* d_costs64;            // [P, S]
     bool profiling;
     std::vector<StepEvents> events;
@@ -379,7 +383,7 @@ extern "C" void sgpmp_destroy(sgpmp_ctx* c) {
     for (int i = 0; i < 2; ++i) { hipFree(c->ms_snap[i]); if (c->ms_read[i]) hipEventDestroy(c->ms_read[i]); }
     if (c->ms_ready) hipEventDestroy(c->ms_ready);
     for (int i = 0; i < 4; ++i) { hipFree(c->d_fval[i]); hipFree(c->d_fgrad[i]); }
-    hipFree(c->d_gscratch); hipFree(c->d_diag); hipFree(c->d_gstatus);
+    hipFree(c->d_gscratch); hipFree(c->d_diag); hipFree(c->d_gstatus); hipFree(c->d_gfine);
     for (void* p : c->owned) hipFree(p);
     for (auto& se : c->events)
         for (auto& e : se.ev) hipEventDestroy(e);
@@ -1602,16 +1606,56 @@ static int gpmp_args(sgpmp_ctx* c, GpmpArgs& a, int* field_terms) {
 }
 
 static int gpmp_alloc(sgpmp_ctx* c, const GpmpArgs& a) {
-    const size_t PT = (size_t)a.P * (a.T - 1);
+    // the field buffers cover the fine states 1 .. T_f - 1 (T_f = T without continuous-time factors): a change of n_sub re-allocates
+    const size_t fine1 = c->gdense.on ? (size_t)c->gdense.k.Tf - 1 : (size_t)a.T - 1;
+    if (fine1 != c->g_fine1) {
+        for (int k = 0; k < 4; ++k) {
+            HIPCHK(hipFree(c->d_fval[k])); c->d_fval[k] = nullptr;
+            HIPCHK(hipFree(c->d_fgrad[k])); c->d_fgrad[k] = nullptr;
+        }
+        HIPCHK(hipFree(c->d_gfine)); c->d_gfine = nullptr;
+        c->g_fine1 = fine1;
+    }
+    const size_t PT = (size_t)a.P * fine1;
     for (int k = 0; k < a.n_fields; ++k) {
         if (!c->d_fval[k]) HIPCHK(hipMalloc(&c->d_fval[k], PT * c->esz));
         if (!c->d_fgrad[k]) HIPCHK(hipMalloc(&c->d_fgrad[k], PT * a.n * c->esz));
     }
+    if (c->gdense.on && a.n_fields > 0 && !c->d_gfine)
+        HIPCHK(hipMalloc(&c->d_gfine, (size_t)a.P * (fine1 + 1) * 2 * a.n * c->esz));
     if (!c->d_gscratch) HIPCHK(hipMalloc(&c->d_gscratch, (size_t)a.P * a.T * 2 * 256 * sizeof(double)));
     if (!c->d_diag) HIPCHK(hipMalloc(&c->d_diag, (size_t)a.T * 2 * a.n * sizeof(double)));
     if (!c->d_gstatus) { HIPCHK(hipMalloc(&c->d_gstatus, sizeof(int))); HIPCHK(hipMemset(c->d_gstatus, 0, sizeof(int))); }
     return SGPMP_OK;
 }
+
+// Continuous-time factors of the linear system (include/sgpmp.h).  The setting lives in the context; linearize and solve pick it up.
+extern "C" int sgpmp_gpmp_set_dense(sgpmp_ctx* c, int n_sub, double dt, double weight, const double* q_lo, const double* q_hi,
+                                    const double* v_max, double sigma_limit) {
+    if (!c) return fail(SGPMP_EINVAL, "sgpmp_gpmp_set_dense: null context");
+    const bool limits = q_lo || q_hi || v_max;
+    if (n_sub < 0 || n_sub > SGPMP_MAX_SUBSTEPS || !(dt > 0.) || !(weight >= 0.) || (limits && !(sigma_limit > 0.)))
+        return fail(SGPMP_EINVAL, "sgpmp_gpmp_set_dense: bad argument (n_sub in [0, 31], dt > 0, weight >= 0, limits need sigma_limit > 0)");
+    if ((n_sub == 0 || weight == 0.) && !limits) {        // nothing to add: the option is off
+        c->gdense.on = false;
+        return SGPMP_OK;
+    }
+    if (!launch_gpmp_fine || !launch_gpmp_dense_diag || !launch_gpmp_dense_solve)
+        return fail(SGPMP_ESTATE, "sgpmp_gpmp_set_dense: this build has no gpmp_dense kernels");
+    GpmpDenseArgs& k = c->gdense.k;
+    std::memset(&k, 0, sizeof(k));
+    k.n_sub = n_sub; k.Tf = (c->dims.traj_len - 1) * (n_sub + 1) + 1; k.dt = dt; k.weight = weight;
+    k.Klim = limits ? 1. / (sigma_limit * sigma_limit) : 0.;
+    k.has_lo = q_lo ? 1 : 0; k.has_hi = q_hi ? 1 : 0; k.has_v = v_max ? 1 : 0;
+    for (int j = 0; j < c->dims.n_dof; ++j) {
+        k.q_lo[j] = q_lo ? q_lo[j] : 0.; k.q_hi[j] = q_hi ? q_hi[j] : 0.; k.v_max[j] = v_max ? v_max[j] : 0.;
+    }
+    c->gdense.on = true;
+    return SGPMP_OK;
+}
+
+static thread_local const char* g_last_gpmp_kernel = "";
+extern "C" const char* sgpmp_last_gpmp_kernel(void) { return g_last_gpmp_kernel; }
 
 extern "C" int sgpmp_gpmp_linearize(sgpmp_ctx* c, const void* means, const void* spheres, int n_spheres,
                                     double* diag_sum, void* stream) {
@@ -1624,6 +1668,36 @@ extern "C" int sgpmp_gpmp_linearize(sgpmp_ctx* c, const void* means, const void*
     if (a.n_fields > 0 && !c->have_chain) return fail(SGPMP_ESTATE, "GPMP: link fields need an FK chain");
     if ((rc = gpmp_alloc(c, a)) != SGPMP_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
+    if (c->gdense.on) {
+        // the same two launches per term on the FINE states 1 .. T_f - 1 of the interpolated means; the rows the solve builds
+        // from them and the limit rows enter diag_sum through gpmp_dense_diag_kernel
+        GpmpDenseArgs& da = c->gdense.k;
+        const int Tf = da.Tf;
+        const long long Bf = (long long)a.P * (Tf - 1);
+        for (int k = 0; k < a.n_fields; ++k) {
+            const CostTerm& t = c->h_prog.terms[ft[k]];
+            if (t.kind == SGPMP_COST_SPHERES && (!spheres || n_spheres < 1))
+                return fail(SGPMP_EINVAL, "LinkDistanceField cost needs obstacle_spheres");
+        }
+        if (a.n_fields > 0 && a.P > 0)
+            HIPCHK(launch_gpmp_fine(c->dims.dtype, a.n, a.T, means, a.P, da.n_sub, da.dt, c->d_gfine, st));
+        for (int k = 0; k < a.n_fields; ++k) {
+            const CostTerm& t = c->h_prog.terms[ft[k]];
+            da.inserted[k] = t.kind == SGPMP_COST_EE_GOAL ? 0 : 1;
+            if (t.kind == SGPMP_COST_EE_GOAL) {
+                HIPCHK(hipMemsetAsync(c->d_fval[k], 0, (size_t)Bf * c->esz, st));
+                HIPCHK(hipMemsetAsync(c->d_fgrad[k], 0, (size_t)Bf * a.n * c->esz, st));
+                HIPCHK(launch_ee_grad(c->dims.dtype, a.n, t, c->d_chain, c->d_gfine, a.P, Tf, Tf - 1, Tf - 2, c->d_fval[k],
+                                      c->d_fgrad[k], st));
+            } else
+                HIPCHK(launch_field_grad(c->dims.dtype, a.n, t, c->d_chain, c->h_chain.n_joints, c->d_gfine, Bf, Tf, spheres,
+                                         n_spheres, c->d_fval[k], c->d_fgrad[k], st));
+            a.f[k].val = c->d_fval[k];
+            a.f[k].grad = c->d_fgrad[k];
+        }
+        if (diag_sum) HIPCHK(launch_gpmp_dense_diag(c->dims.dtype, a, da, means, diag_sum, st));
+        return SGPMP_OK;
+    }
     const long long B = (long long)a.P * (a.T - 1);
     for (int k = 0; k < a.n_fields; ++k) {
         const CostTerm& t = c->h_prog.terms[ft[k]];
@@ -1661,7 +1735,21 @@ extern "C" int sgpmp_gpmp_solve(sgpmp_ctx* c, void* means, const double* diag_su
     a.status = c->d_gstatus;
     a.inv_particles = 1.0 / (double)(c->dims.num_particles_global > 0 ? c->dims.num_particles_global : a.P);
     hipStream_t st = (hipStream_t)stream;
-    HIPCHK(launch_gpmp_solve(c->dims.dtype, a, means, d_theta, costs, st, c->tg.gpmp_cholesky != 0));
+    if (c->gdense.on) {
+        if (c->g_fine1 != (size_t)c->gdense.k.Tf - 1)
+            return fail(SGPMP_ESTATE, "sgpmp_gpmp_solve: call sgpmp_gpmp_linearize after sgpmp_gpmp_set_dense");
+        for (int k = 0; k < a.n_fields; ++k)
+            c->gdense.k.inserted[k] = c->h_prog.terms[ft[k]].kind == SGPMP_COST_EE_GOAL ? 0 : 1;
+        HIPCHK(launch_gpmp_dense_solve(c->dims.dtype, a, c->gdense.k, means, d_theta, costs, st));
+        g_last_gpmp_kernel = "gpmp_dense_solve_kernel";
+    } else {
+        if (c->g_fine1 != (size_t)a.T - 1)
+            return fail(SGPMP_ESTATE, "sgpmp_gpmp_solve: call sgpmp_gpmp_linearize after sgpmp_gpmp_set_dense");
+        // (launch_gpmp_solve's own choice: the register-resident kernel for the joint counts it is instantiated for)
+        const bool thomas = !c->tg.gpmp_cholesky && (a.n == 2 || a.n == 3 || a.n == 6 || a.n == 7);
+        HIPCHK(launch_gpmp_solve(c->dims.dtype, a, means, d_theta, costs, st, c->tg.gpmp_cholesky != 0));
+        g_last_gpmp_kernel = thomas ? "gpmp_thomas_kernel" : "gpmp_solve_kernel";
+    }
     int status = 0;                                   // synchronous, like sgpmp_set_prior: GPMP is not the hot path
     HIPCHK(hipMemcpyAsync(&status, c->d_gstatus, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));

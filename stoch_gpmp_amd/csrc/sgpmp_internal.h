@@ -363,6 +363,33 @@ struct GpmpArgs {
 hipError_t launch_gpmp_diag(int dtype, const GpmpArgs& a, double* diag_sum, hipStream_t stream);
 hipError_t launch_gpmp_solve(int dtype, const GpmpArgs& a, void* means, void* d_theta, void* costs,
                              hipStream_t stream, bool cholesky = false);
+
+// The Hermite weights of the dense trajectories as a plain table (traj_dense.hip: hermite_coefs, the weights hermite_state
+// applies): per sub-step m = 1 .. k, q = c0 q_i + c1 v_i + c2 q_{i+1} + c3 v_{i+1}, v = c4 .. c7 likewise, in the context's dtype.
+template <typename real>
+struct HermiteTab { real c[SGPMP_MAX_SUBSTEPS][8]; };
+void hermite_table(int dtype, int n_sub, double dt, void* out);
+
+// GPMP with continuous-time factors (gpmp_dense.hip): collision rows on the n_sub inserted states of every interval and limit
+// rows on all fine states, beside GpmpArgs.  With it GpmpFieldK::val / grad are [P, T_f - 1] / [P, T_f - 1, n] over the fine
+// states 1 .. T_f - 1.
+struct GpmpDenseArgs {
+    int n_sub, Tf;                // k states inserted per interval; T_f = (T - 1)(k + 1) + 1
+    double dt;                    // of the interpolation
+    double weight;                // scales the precision of the inserted states' collision rows
+    double Klim;                  // 1 / sigma_limit^2, 0: no limit rows
+    int has_lo, has_hi, has_v;
+    double q_lo[SGPMP_MAX_DOF], q_hi[SGPMP_MAX_DOF], v_max[SGPMP_MAX_DOF];
+    int inserted[4];              // link-field term k has rows on the inserted states (an end-effector goal has its one row)
+};
+// api.hip is also linked WITHOUT the kernel files (tests/host_asan: the host bookkeeping over a stub runtime): what it calls
+// of gpmp_dense.hip is declared weak, and sgpmp_gpmp_set_dense refuses where the definitions are absent.
+hipError_t launch_gpmp_fine(int dtype, int n, int T, const void* means, long long P, int n_sub, double dt, void* fine,
+                            hipStream_t stream) __attribute__((weak));
+hipError_t launch_gpmp_dense_diag(int dtype, const GpmpArgs& a, const GpmpDenseArgs& da, const void* means, double* diag_sum,
+                                  hipStream_t stream) __attribute__((weak));
+hipError_t launch_gpmp_dense_solve(int dtype, const GpmpArgs& a, const GpmpDenseArgs& da, void* means, void* d_theta,
+                                   void* costs, hipStream_t stream) __attribute__((weak));
 hipError_t launch_link_dist(int dtype, const void* frames, long long batch, int n_links, const void* spheres,
                             int n_other, int mode, double buffer, void* out, hipStream_t stream);
 hipError_t launch_fk(int dtype, int n, const ChainDev* d_chain, int n_links, const void* q,

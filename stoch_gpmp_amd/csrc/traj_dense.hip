@@ -326,6 +326,19 @@ static hipError_t launch_interpolate(int n, int T, const void* trajs, long long 
     return hipGetLastError();
 }
 
+// hermite_coefs as a plain table real[SGPMP_MAX_SUBSTEPS][8] of the context's dtype, for gpmp_dense.hip's rows
+void hermite_table(int dtype, int n_sub, double dt, void* out) {
+    if (dtype == SGPMP_F64) { const HermiteK<double> H = hermite_coefs<double>(n_sub, dt); std::memcpy(out, &H, sizeof(H)); }
+    else { const HermiteK<float> H = hermite_coefs<float>(n_sub, dt); std::memcpy(out, &H, sizeof(H)); }
+}
+
+// the particle means on the fine grid for sgpmp_gpmp_linearize (api.hip): the launch of sgpmp_interpolate
+hipError_t launch_gpmp_fine(int dtype, int n, int T, const void* means, long long P, int n_sub, double dt, void* fine,
+                            hipStream_t stream) {
+    return dtype == SGPMP_F64 ? launch_interpolate<double>(n, T, means, P, n_sub, dt, fine, stream)
+                              : launch_interpolate<float>(n, T, means, P, n_sub, dt, fine, stream);
+}
+
 template <typename real>
 static TermK<real> grid_termk(const CostTerm& s) {             // the fields grid_value reads
     TermK<real> k;

@@ -1,5 +1,6 @@
 """Host-side arithmetic of the dense (GP-interpolated) trajectories: index bookkeeping and the interpolation weights that
-`sgpmp_interpolate` / `sgpmp_validate` / `sgpmp_dense_cost` / `sgpmp_dense_cost_grad` (csrc/traj_dense.hip) apply on the GPU.  numpy only, no GPU, no library.
+`sgpmp_interpolate` / `sgpmp_validate` / `sgpmp_dense_cost` / `sgpmp_dense_cost_grad` (csrc/traj_dense.hip) apply on the GPU, and the
+rows `sgpmp_gpmp_set_dense` adds to GPMP's linear system (csrc/gpmp_dense.hip).  numpy only, no GPU, no library.
 
 Between two support states x_i = (q_i, v_i) and x_{i+1}, `dt` apart, the posterior mean of the constant-velocity GP prior is
 
@@ -133,3 +134,42 @@ def limit_penalty_grad(fine, q_limits=None, v_limits=None, sigma_limit=None):
     if v_limits is not None:
         out[..., n:] += np.sign(v) * np.maximum(np.abs(v) - np.asarray(v_limits, dtype=np.float64), 0.)
     return out * (2. / float(sigma_limit) ** 2)
+
+
+def gn_rows(trajs, n_sub, dt, q_limits=None, v_limits=None):
+    """The scalar rows the continuous-time factors add to GPMP's linear system (`sgpmp_gpmp_set_dense`; convention of the
+    reference: A row = -d error / d x, b = error), as their nonzero coefficients, in fp64.  Fine state f of trajs [..., T, 2n]
+    lies in interval i = `interval[f]` at sub-step `m[f]`; every row at f touches x_i and x_{i+1} only (the last state is
+    written as m = n_sub + 1 of interval T - 2: Lambda = 0, Psi = I).  Returns a dict with
+      'interval', 'm'  [T_f] int64;
+      'collision'      [T_f, 4]: a collision row of a field with gradient g = d field / d q_f has the entries
+                       -collision[f] (x) g on (q_i, v_i, q_{i+1}, v_{i+1}) -- row 0 of (Lambda[m], Psi[m]); b = the field;
+      'q_lo', 'q_hi', 'v_max' (the limits that are given): (A [..., T_f, n, 4], b [..., T_f, n]), the row of degree of freedom j
+                       at state f: its entries on dof j of (q_i, v_i, q_{i+1}, v_{i+1}) and its error max(0, q_lo - q),
+                       max(0, q - q_hi), max(0, |q'| - v_max); an inactive row is a zero row.
+    q_limits = (lower [n], upper [n]), either may be None; v_limits [n]."""
+    x = np.asarray(trajs, dtype=np.float64)
+    T, n = x.shape[-2], x.shape[-1] // 2
+    n_sub = int(n_sub)
+    k1 = n_sub + 1
+    lam, psi = hermite_weights(n_sub, dt)
+    P4 = np.concatenate([np.stack([lam[:, 0, 0], lam[:, 0, 1], psi[:, 0, 0], psi[:, 0, 1]], axis=1), [[0., 0., 1., 0.]]])
+    V4 = np.concatenate([np.stack([lam[:, 1, 0], lam[:, 1, 1], psi[:, 1, 0], psi[:, 1, 1]], axis=1), [[0., 0., 0., 1.]]])
+    f = np.arange(fine_length(T, n_sub), dtype=np.int64)
+    interval = np.minimum(f // k1, T - 2)
+    m = f - interval * k1
+    out = {'interval': interval, 'm': m, 'collision': P4[m]}
+    fine = interpolate(x, n_sub, dt)
+    q, v = fine[..., :n], fine[..., n:]
+    cp, cv = P4[m][:, None, :], V4[m][:, None, :]                   # [T_f, 1, 4]
+    q_lo, q_hi = (None, None) if q_limits is None else q_limits
+    if q_lo is not None:
+        e = np.maximum(np.asarray(q_lo, dtype=np.float64) - q, 0.)
+        out['q_lo'] = ((e > 0.)[..., None] * cp, e)
+    if q_hi is not None:
+        e = np.maximum(q - np.asarray(q_hi, dtype=np.float64), 0.)
+        out['q_hi'] = ((e > 0.)[..., None] * -cp, e)
+    if v_limits is not None:
+        e = np.maximum(np.abs(v) - np.asarray(v_limits, dtype=np.float64), 0.)
+        out['v_max'] = (-((e > 0.) * np.sign(v))[..., None] * cv, e)
+    return out

@@ -673,6 +673,19 @@ class Engine:
             L.check(self.lib.sgpmp_gpmp_linearize(self._ctx, L.ptr(means), L.ptr(spheres), n_sph,
                                                   L.ptr(diag_sum), L.stream_ptr()))
 
+    def gpmp_set_dense(self, n_sub, dt, weight=1.0, q_limits=None, v_limits=None, sigma_limit=None):
+        """Continuous-time factors in the Gauss-Newton system: collision rows on the `n_sub` GP-interpolated states per interval
+        (precision weight x the term's) and joint / velocity limit rows on all fine states (include/sgpmp.h:
+        sgpmp_gpmp_set_dense; numpy twin of the rows: dense.gn_rows).  gpmp_linearize / gpmp_solve pick the setting up;
+        n_sub = 0 or weight = 0 without limits switches it off."""
+        q_lo, q_hi, v_max = self._host_limits(q_limits, v_limits)
+        L.check(self.lib.sgpmp_gpmp_set_dense(self._ctx, int(n_sub), float(dt), float(weight), q_lo, q_hi, v_max,
+                                              0.0 if sigma_limit is None else float(sigma_limit)))
+
+    def last_gpmp_kernel(self):
+        """Name of the solve kernel this thread's last gpmp_solve() launched ("" before the first)."""
+        return self.lib.sgpmp_last_gpmp_kernel().decode()
+
     def gpmp_solve(self, means, delta, step_size, diag_sum=None, d_theta=None, costs=None):
         """Block-tridiagonal Gauss-Newton solve + in-place update of `means`; -> (d_theta, costs)."""
         self._chk(means, "means")

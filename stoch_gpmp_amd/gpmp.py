@@ -6,6 +6,9 @@ solves it densely.  Here one call pair does a step on the GPU: `sgpmp_gpmp_linea
 field Jacobians at every waypoint) and `sgpmp_gpmp_solve` (per particle, block-tridiagonal assembly
 and block Cholesky on the fp64 matrix cores, means updated in place) -- see csrc/gpmp.hip.
 
+`set_dense_cost` / `GPMP(dense_cost=...)` add continuous-time factors to that system -- collision rows on the GP-interpolated
+states between the waypoints, joint and velocity limit rows on all fine states -- see csrc/gpmp_dense.hip.
+
 Divergence, on purpose: `solver_params['method'] = 'cholesky'` SOLVES the system here.  The reference's
 branch passes `upper=False` with `l.mT` to its second triangular solve (planner.py:634-636), which makes
 torch read only the diagonal of the factor, so it returns diag(L)^-1 L^-1 g instead of the solution;
@@ -46,10 +49,20 @@ class GPMP(StochGPMP):
                          tensor_args=tensor_args, **kwargs)
 
     def set_dense_cost(self, setting=None, **kw):
-        """The continuous-time term enters StochGPMP's sampled cost only; the Gauss-Newton linear system has no such factor."""
-        if setting is not None or kw:
-            raise NotImplementedError("GPMP: dense_cost is an option of StochGPMP (no continuous-time factor in the linear system)")
-        self._dense = None
+        """Continuous-time factors in the Gauss-Newton system, with StochGPMP's setting dict(n_sub=4, weight=1.0, q_limits=None,
+        v_limits=None, sigma_limit=None) (or the same as keywords) and its validation: every SPHERES / SELF term of the cost list
+        gets a row at each of the n_sub GP-interpolated states per interval (precision weight x the term's), and every degree of
+        freedom joint (q_limits = (lower, upper)) / velocity (v_limits) limit rows with precision 1/sigma_limit^2 at all fine
+        states (include/sgpmp.h: sgpmp_gpmp_set_dense; the rows: dense.gn_rows).  The step then solves a block-tridiagonal system
+        with a per-interval sub-diagonal block (csrc/gpmp_dense.hip).  None switches it off: the planner is then bit for bit the
+        one without the option."""
+        super().set_dense_cost(setting, **kw)
+        c = self._dense
+        if c is None:
+            self._engine.gpmp_set_dense(0, self.dt, weight=0.)
+        else:
+            self._engine.gpmp_set_dense(c['n_sub'], self.dt, weight=c['weight'], q_limits=c['q_limits'],
+                                        v_limits=c['v_limits'], sigma_limit=c['sigma_limit'])
 
     def get_dist(self, start_K, gp_K, goal_K, state_init, particle_means=None, goal_states=None):
         """planner.py:479-501: a stand-alone MultiMPPrior of this problem (the same object StochGPMP.get_prior_dist builds)."""
