@@ -59,13 +59,19 @@ enum {
     SGPMP_COST_GRID = 3,        /* CostCollision + ObstacleMap           cost_functions.py:247-261, obst_map.py:164-185 */
     SGPMP_COST_SPHERES = 4,     /* CostCollision + LinkDistanceField     fields.py:63-86                   */
     SGPMP_COST_SELF = 5,        /* CostCollision + LinkSelfDistanceField fields.py:114-124                 */
-    SGPMP_COST_EE_GOAL = 6      /* CostGoal + EESE3DistanceField         cost_functions.py:282-321, fields.py:130-153
+    SGPMP_COST_EE_GOAL = 6,     /* CostGoal + EESE3DistanceField         cost_functions.py:282-321, fields.py:130-153
                                    (SE3_distance itself is third-party and un-vendored: DESIGN.md)      */
+    SGPMP_COST_GRID_SDF = 7     /* CostCollision + GridDistanceField: hinge on a signed-distance grid (no reference
+                                   counterpart; defined at sgpmp_grid_sdf_build below)                   */
 };
 enum { SGPMP_FIELD_RBF = 0, SGPMP_FIELD_SDF = 1, SGPMP_FIELD_OCCUPANCY = 2 };
 #define SGPMP_FLAG_GP_START 1      /* GP term includes the start-state unary factor (CostGP)  */
 #define SGPMP_FLAG_SDF_CLAMP 16    /* LinkDistanceField(clamp_sdf=True)                       */
 #define SGPMP_FLAG_EE_SQUARE 32    /* EESE3DistanceField(square=True)                         */
+#define SGPMP_FLAG_GRID_DISTANCE 64 /* GRID_SDF: sgpmp_field_grad returns the interpolated distance d and dd/d(x, y) instead of
+                                      the hinge and its gradient (GridDistanceField.compute_distance).  A query flag, not a cost:
+                                      allowed only in a cost list whose single term is this one (else SGPMP_EINVAL), and the
+                                      GPMP linearisation refuses a term that carries it */
 
 #define SGPMP_MAX_TERMS 8
 #define SGPMP_MAX_JOINTS 16
@@ -88,17 +94,19 @@ typedef struct sgpmp_dims {
 
 typedef struct sgpmp_cost_desc {
     int32_t kind;                  /* SGPMP_COST_*                                                */
-    int32_t flags;                 /* GP: SGPMP_FLAG_GP_START; SPHERES: SGPMP_FIELD_* | SGPMP_FLAG_SDF_CLAMP */
+    int32_t flags;                 /* GP: SGPMP_FLAG_GP_START; SPHERES: SGPMP_FIELD_* | SGPMP_FLAG_SDF_CLAMP;
+                                      GRID_SDF: SGPMP_FLAG_GRID_DISTANCE                           */
     double sigma;                  /* GP: sigma_gp; GOAL_PRIOR: sigma_goal_prior; collision: sigma_coll */
-    double sigma2;                 /* GP: sigma_start; SELF: margin                               */
+    double sigma2;                 /* GP: sigma_start; SELF: margin; GRID_SDF: margin (>= 0)      */
     double dt;                     /* GP: time step                                               */
     const void* data;              /* GP: HOST double[d] start state; GOAL_PRIOR: HOST double[G*d]
                                       goal states; GRID: DEVICE grid [dim0,dim1] in ctx dtype;
+                                      GRID_SDF: DEVICE sdf [dim0 = ny, dim1 = nx] in ctx dtype;
                                       EE_GOAL: HOST double[16] target frame (row-major 4x4), with
                                       p0 = w_pos, p1 = w_rot                                      */
     int32_t dim0, dim1;            /* GOAL_PRIOR: G, nppg*S of the cost (cost_functions.py:379);
-                                      GRID: map.shape[0], map.shape[1]                            */
-    double p0, p1, p2;             /* GRID: cell_size, c_offset[0], c_offset[1] (obst_map.py:129-140) */
+                                      GRID, GRID_SDF: map.shape[0], map.shape[1]                  */
+    double p0, p1, p2;             /* GRID, GRID_SDF: cell_size, c_offset[0], c_offset[1] (obst_map.py:129-140) */
     int32_t num_interpolate;       /* fields.py:32,94                                             */
     int32_t interp_lo, interp_hi;  /* link_interpolate_range                                      */
     int32_t reserved;
@@ -457,6 +465,41 @@ int sgpmp_field_grad(sgpmp_ctx* ctx, int term, const void* q, int64_t batch, con
  * f = i (k + 1) + m at s = m / (k + 1) of interval i; support states (m = 0, and f = T_f - 1) are copied, not computed.  Both
  * entry points evaluate the fine states with the same device function (csrc/traj_dense.hip: hermite_state), bit for bit. */
 #define SGPMP_MAX_SUBSTEPS 31
+
+/* ---- signed-distance grid field (SGPMP_COST_GRID_SDF) -------------------------------------------
+ * A smooth collision field for planar map scenes: the occupancy grid's exact Euclidean signed distance, interpolated
+ * bilinearly, under the GPMP hinge.  No reference counterpart (its ObstacleMap is occupancy only).
+ *
+ * sgpmp_grid_sdf_build: occ [ny, nx] (DEVICE, ctx dtype; a cell is occupied when (double)occ > threshold) -> sdf [ny, nx]
+ * (DEVICE, ctx dtype), the signed distance at cell centres in world units.  For a free cell a, D(a) = min over occupied cells b
+ * of the Euclidean distance between the index pairs and sdf = (D - 0.5) * cell; for an occupied cell D is taken over the free
+ * cells and sdf = -(D - 0.5) * cell: the zero level sits on cell edges.  Exact: squared distances are integers, one correctly
+ * rounded square root in double, then the subtract and the multiply in that order, then the conversion to the ctx dtype.  A map
+ * with no occupied cell gives +cap everywhere, one with no free cell -cap, cap = cell * (nx + ny); never infinite.
+ * 1 <= nx, ny <= 4096 and cell > 0, else SGPMP_EINVAL (before any launch).  Stream-ordered, two launches, no host copy of the
+ * map, no allocation; occ and sdf must not overlap.
+ *
+ * The term: sgpmp_cost_desc { kind = SGPMP_COST_GRID_SDF, data = sdf, dim0 = ny, dim1 = nx, p0 = cell, p1, p2 = the offsets
+ * (ox, oy) of SGPMP_COST_GRID, sigma -> K = 1 / sigma^2, sigma2 = margin >= 0 }; needs n_dof >= 2, the point is (q[0], q[1]).
+ *   u = x * (1 / cell) + ox - 0.5, v = y * (1 / cell) + oy - 0.5   (multiply and add rounded separately, as the GRID lookup)
+ *   i0 = floor(u), fx = u - i0, j0 = floor(v), fy = v - j0; i0, i0 + 1 clamped to [0, nx - 1], j0, j0 + 1 to [0, ny - 1]
+ *   d = (1 - fy) ((1 - fx) s00 + fx s10) + fy ((1 - fx) s01 + fx s11),  s[j][i] = sdf[j * nx + i]
+ *   field h = margin - d where that is > 0, else 0;  dh/d(x, y) = -(dd/dx, dd/dy) where h > 0, exactly 0 elsewhere,
+ *   dd/dx = ((1 - fy)(s10 - s00) + fy (s11 - s01)) * (1 / cell),  dd/dy = ((1 - fx)(s01 - s00) + fx (s11 - s10)) * (1 / cell)
+ *   (the reciprocal the first operation multiplies by: not a division).
+ * x is clamped by the x extent (dim1) and y by the y extent (dim0): the GRID lookup's reference-inherited clamp of x by dim0 is
+ * NOT copied.  Outside the map the clamp makes the derivative in that direction zero.  A non-finite x or y gives NaN in the
+ * value and in the gradient.
+ * In a cost list the term is K * sum over t = 1 .. T-1 of h(q_t[0], q_t[1]) (SGPMP_COST_GRID's range) in sgpmp_cost_eval /
+ * sgpmp_step (sampler + generic sweep + update: no fused launch takes it), one of the collision terms of sgpmp_dense_cost and
+ * sgpmp_dense_cost_grad (differentiable; not together with link-field terms in the gradient: SGPMP_EINVAL), a field of
+ * sgpmp_field_grad (no FK chain needed: q [B, n] -> value [B], grad [B, n], entries >= 2 zero; SGPMP_ESTATE in a build without
+ * the kernel) and one of the four field slots of sgpmp_gpmp_linearize (one row per waypoint 1 .. T-1, error h, precision K,
+ * A = -dh/dq on entries 0 and 1; with sgpmp_gpmp_set_dense on the fine states).  sgpmp_validate's occupancy column still needs
+ * a SGPMP_COST_GRID term. */
+int sgpmp_grid_sdf_build(sgpmp_ctx* ctx, const void* occ, int ny, int nx, double cell, double threshold, void* sdf,
+                         void* stream);
+
 /* trajs [B,T,d] -> out [B,T_f,d], ctx dtype, T = dims.traj_len. */
 int sgpmp_interpolate(sgpmp_ctx* ctx, const void* trajs, int64_t batch, int n_sub, double dt, void* out, void* stream);
 /* Per trajectory, over ALL T_f fine states (never written to memory): values [B,4] ctx dtype, where [B,4] int32 = the first fine

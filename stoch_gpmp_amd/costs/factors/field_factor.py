@@ -19,7 +19,7 @@ class FieldFactor:
         if calc_jacobian:
             if fk_chain is None:
                 fk_chain = getattr(field, "fk_chain", None)
-            if fk_chain is None:
+            if fk_chain is None and getattr(field, "needs_fk_chain", True):
                 raise ValueError("calc_jacobian=True (the default, as in the reference) needs fk_chain= (the URDF chain of the "
                                  "composite's FK): the analytic Jacobian replaces the reference's autograd pass")
             if not hasattr(field, "compute_cost_and_grad"):

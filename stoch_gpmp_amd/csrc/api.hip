@@ -673,6 +673,20 @@ extern "C" int sgpmp_set_costs(sgpmp_ctx* c, const sgpmp_cost_desc* descs, int n
                 t.inv_cell = 1. / s.p0;                           // obst_map.py:172
                 t.off_x = s.p1; t.off_y = s.p2;
                 break;
+            case SGPMP_COST_GRID_SDF:
+                if (!s.data || s.dim0 < 1 || s.dim1 < 1 || !(s.p0 > 0.) || !(s.sigma2 >= 0.))
+                    return fail(SGPMP_EINVAL, "sgpmp_set_costs: grid distance term needs a device sdf grid, cell size and margin >= 0");
+                if (c->dims.n_dof < 2)
+                    return fail(SGPMP_EINVAL, "sgpmp_set_costs: grid distance term needs n_dof >= 2");
+                if ((s.flags & SGPMP_FLAG_GRID_DISTANCE) && n_desc != 1)
+                    return fail(SGPMP_EINVAL, "sgpmp_set_costs: SGPMP_FLAG_GRID_DISTANCE is a query flag for sgpmp_field_grad: "
+                                              "the term must be the cost list's only one");
+                t.dev_data = s.data;
+                t.dim0 = s.dim0; t.dim1 = s.dim1;
+                t.inv_cell = 1. / s.p0;
+                t.off_x = s.p1; t.off_y = s.p2;
+                t.K2 = s.sigma2;                                  // the hinge's margin (TermK::K2)
+                break;
             case SGPMP_COST_SPHERES:
             case SGPMP_COST_SELF:
                 if (s.num_interpolate < 0 || s.num_interpolate > SGPMP_MAX_INTERP)
@@ -959,6 +973,7 @@ int sgpmp_ctx_view(sgpmp_ctx* c, SgpmpCtxView* out) {
     return rc;
 }
 int sgpmp_set_error(int code, const char* msg) { return fail(code, msg); }
+int sgpmp_ctx_dtype(const sgpmp_ctx* c) { return c->dims.dtype; }
 
 extern "C" int sgpmp_sample(sgpmp_ctx* c, int which, uint64_t seed, uint64_t draw, const void* means,
                             int n_modes, int mode_offset, int n_samples, const void* eps, int eps_modes,
@@ -1543,6 +1558,12 @@ extern "C" int sgpmp_field_grad(sgpmp_ctx* c, int term, const void* q, int64_t b
     if (!c || !q || !grad || batch < 0) return fail(SGPMP_EINVAL, "sgpmp_field_grad: bad argument");
     if (!c->have_costs || term < 0 || term >= c->h_prog.n_terms)
         return fail(SGPMP_EINVAL, "sgpmp_field_grad: bad term index");
+    if (c->h_prog.terms[term].kind == SGPMP_COST_GRID_SDF) {     // a field of the planar point itself: no FK chain
+        if (!launch_grid_sdf_grad) return fail(SGPMP_ESTATE, "sgpmp_field_grad: this build has no grid_sdf kernels");
+        HIPCHK(launch_grid_sdf_grad(c->dims.dtype, c->dims.n_dof, c->h_prog.terms[term], q, batch, 0, value, grad,
+                                    (hipStream_t)stream));
+        return SGPMP_OK;
+    }
     if (!c->have_chain) return fail(SGPMP_EINVAL, "sgpmp_field_grad: no FK chain (sgpmp_set_fk)");
     int rc;
     if ((rc = finalize_program(c)) != SGPMP_OK) return rc;
@@ -1591,6 +1612,9 @@ static int gpmp_args(sgpmp_ctx* c, GpmpArgs& a, int* field_terms) {
                 /* fall through */
             case SGPMP_COST_EE_GOAL:                      // (a field row on the last waypoint only)
             case SGPMP_COST_SELF:
+            case SGPMP_COST_GRID_SDF:                     // (a field of the planar point: no FK chain)
+                if (t.kind == SGPMP_COST_GRID_SDF && (t.flags & SGPMP_FLAG_GRID_DISTANCE))
+                    return fail(SGPMP_EINVAL, "GPMP: a grid distance term with SGPMP_FLAG_GRID_DISTANCE is a query, not a cost");
                 if (a.n_fields == 4) return fail(SGPMP_EINVAL, "GPMP: more than 4 link-field terms");
                 field_terms[a.n_fields] = i;
                 a.f[a.n_fields].K = t.K;
@@ -1665,7 +1689,12 @@ extern "C" int sgpmp_gpmp_linearize(sgpmp_ctx* c, const void* means, const void*
     GpmpArgs a;
     int ft[4];
     if ((rc = gpmp_args(c, a, ft)) != SGPMP_OK) return rc;
-    if (a.n_fields > 0 && !c->have_chain) return fail(SGPMP_ESTATE, "GPMP: link fields need an FK chain");
+    for (int k = 0; k < a.n_fields; ++k) {
+        const int kind = c->h_prog.terms[ft[k]].kind;
+        if (kind != SGPMP_COST_GRID_SDF && !c->have_chain) return fail(SGPMP_ESTATE, "GPMP: link fields need an FK chain");
+        if (kind == SGPMP_COST_GRID_SDF && !launch_grid_sdf_grad)
+            return fail(SGPMP_ESTATE, "GPMP: this build has no grid_sdf kernels");
+    }
     if ((rc = gpmp_alloc(c, a)) != SGPMP_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (c->gdense.on) {
@@ -1689,7 +1718,9 @@ extern "C" int sgpmp_gpmp_linearize(sgpmp_ctx* c, const void* means, const void*
                 HIPCHK(hipMemsetAsync(c->d_fgrad[k], 0, (size_t)Bf * a.n * c->esz, st));
                 HIPCHK(launch_ee_grad(c->dims.dtype, a.n, t, c->d_chain, c->d_gfine, a.P, Tf, Tf - 1, Tf - 2, c->d_fval[k],
                                       c->d_fgrad[k], st));
-            } else
+            } else if (t.kind == SGPMP_COST_GRID_SDF)
+                HIPCHK(launch_grid_sdf_grad(c->dims.dtype, a.n, t, c->d_gfine, Bf, Tf, c->d_fval[k], c->d_fgrad[k], st));
+            else
                 HIPCHK(launch_field_grad(c->dims.dtype, a.n, t, c->d_chain, c->h_chain.n_joints, c->d_gfine, Bf, Tf, spheres,
                                          n_spheres, c->d_fval[k], c->d_fgrad[k], st));
             a.f[k].val = c->d_fval[k];
@@ -1710,7 +1741,9 @@ extern "C" int sgpmp_gpmp_linearize(sgpmp_ctx* c, const void* means, const void*
             HIPCHK(hipMemsetAsync(c->d_fgrad[k], 0, (size_t)B * a.n * c->esz, st));
             HIPCHK(launch_ee_grad(c->dims.dtype, a.n, t, c->d_chain, means, a.P, a.T, a.T - 1, a.T - 2, c->d_fval[k],
                                   c->d_fgrad[k], st));
-        } else
+        } else if (t.kind == SGPMP_COST_GRID_SDF)
+            HIPCHK(launch_grid_sdf_grad(c->dims.dtype, a.n, t, means, B, a.T, c->d_fval[k], c->d_fgrad[k], st));
+        else
         HIPCHK(launch_field_grad(c->dims.dtype, a.n, t, c->d_chain, c->h_chain.n_joints, means, B, a.T, spheres,
                                  n_spheres, c->d_fval[k], c->d_fgrad[k], st));
         a.f[k].val = c->d_fval[k];

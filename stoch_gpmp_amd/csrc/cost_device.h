@@ -161,6 +161,49 @@ __device__ __forceinline__ real grid_value(const TermK<real>& tm, real x, real y
     return grid[(size_t)iy * tm.dim1 + ix];
 }
 
+// ---------------------------------------------------------------------------------- signed-distance grid field
+// SGPMP_COST_GRID_SDF (include/sgpmp.h has the definition).  grid_sdf_distance: the bilinear interpolation d between the cell
+// centres of the signed-distance grid tm.dev_data [dim0 = ny][dim1 = nx], clamp-to-edge, with GRAD also dd/dx, dd/dy.  The
+// first two operations are grid_value's; x is clamped by the x extent dim1 and y by dim0 (grid_value's reference-inherited
+// clamp of x by dim0 is not copied).  A non-finite x or y gives d = NaN: the index clamp may drop the NaN (fmin / fmax do), the
+// fractions keep it.
+template <typename real, bool GRAD>
+__device__ __forceinline__ real grid_sdf_distance(const TermK<real>& tm, real x, real y, real* ddx, real* ddy) {
+    using O = RealOps<real>;
+    const real u = O::add_rn(O::mul_rn(x, tm.inv_cell), tm.off_x) - (real)0.5;
+    const real v = O::add_rn(O::mul_rn(y, tm.inv_cell), tm.off_y) - (real)0.5;
+    const real fu = O::floor_(u), fv = O::floor_(v);
+    const real fx = u - fu, fy = v - fv;
+    const real hx = (real)(tm.dim1 - 1), hy = (real)(tm.dim0 - 1);
+    const int i0 = (int)fmin(fmax(fu, (real)0), hx), i1 = (int)fmin(fmax(fu + (real)1, (real)0), hx);   // clamp in float first
+    const int j0 = (int)fmin(fmax(fv, (real)0), hy), j1 = (int)fmin(fmax(fv + (real)1, (real)0), hy);
+    const real* sdf = (const real*)tm.dev_data;
+    const real s00 = sdf[(size_t)j0 * tm.dim1 + i0], s10 = sdf[(size_t)j0 * tm.dim1 + i1];
+    const real s01 = sdf[(size_t)j1 * tm.dim1 + i0], s11 = sdf[(size_t)j1 * tm.dim1 + i1];
+    const real ax = (real)1 - fx, ay = (real)1 - fy;
+    if constexpr (GRAD) {
+        *ddx = (ay * (s10 - s00) + fy * (s11 - s01)) * tm.inv_cell;
+        *ddy = (ax * (s01 - s00) + fx * (s11 - s10)) * tm.inv_cell;
+    }
+    return ay * (ax * s00 + fx * s10) + fy * (ax * s01 + fx * s11);
+}
+// grid_sdf_field: the hinge h = margin - d where positive, else 0, with GRAD also dh/dx, dh/dy (exactly zero where the hinge is
+// inactive).  The one function every consumer of the term calls -- sweep, dense cost and its gradient, sgpmp_field_grad, the
+// GPMP rows: one definition, one operation order.  (Not a promise of equal bits across kernels: the compiler may contract a
+// multiply and an add into an FMA differently at each place it inlines this.)  Selects that keep a NaN: it reaches the value and
+// both derivatives.
+template <typename real, bool GRAD>
+__device__ __forceinline__ real grid_sdf_field(const TermK<real>& tm, real x, real y, real* gx, real* gy) {
+    real ddx = 0, ddy = 0;
+    const real e = tm.K2 - grid_sdf_distance<real, GRAD>(tm, x, y, &ddx, &ddy);   // K2: the margin
+    const bool off = e <= (real)0;                         // (false for a NaN: it passes through)
+    if constexpr (GRAD) {
+        *gx = off ? (real)0 : (e == e ? -ddx : e);
+        *gy = off ? (real)0 : (e == e ? -ddy : e);
+    }
+    return off ? (real)0 : e;
+}
+
 // ---------------------------------------------------------------------------------- generic FK (LDS)
 // Positions of all link frames for joint vector q, written to LDS column `col` (SoA, `stride`
 // reals between consecutive scalars).  H_child = H_parent * Trans(xyz) * RPY * Rz(q).

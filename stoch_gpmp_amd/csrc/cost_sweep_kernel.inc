@@ -463,6 +463,9 @@ __device__ __forceinline__ void cost_sweep_body(const CostArgs<real>& a, const P
                 } else if (tm.kind == SGPMP_COST_GRID) {
                     const real gv = grid_value<real>(tm, x[0], x[N > 1 ? 1 : 0]);
                     if (inner) part += tm.K * gv;
+                } else if (tm.kind == SGPMP_COST_GRID_SDF) {
+                    const real h = grid_sdf_field<real, false>(tm, x[0], x[N > 1 ? 1 : 0], nullptr, nullptr);
+                    if (inner) part += tm.K * h;
                 }
             }
         }

@@ -172,6 +172,7 @@ struct SgpmpCtxView {
 // fills *out; runs finalize_program when costs are set and returns its status (out->prog stays null when it fails)
 int sgpmp_ctx_view(sgpmp_ctx* c, SgpmpCtxView* out);
 int sgpmp_set_error(int code, const char* msg);
+int sgpmp_ctx_dtype(const sgpmp_ctx* c);          // SGPMP_F32 | SGPMP_F64: all an entry point without a cost program needs
 
 // ---------------------------------------------------------------------------------- run-time chain kernels (chain_rtc.hip)
 struct RtcChain;
@@ -390,6 +391,11 @@ hipError_t launch_gpmp_dense_diag(int dtype, const GpmpArgs& a, const GpmpDenseA
                                   hipStream_t stream) __attribute__((weak));
 hipError_t launch_gpmp_dense_solve(int dtype, const GpmpArgs& a, const GpmpDenseArgs& da, void* means, void* d_theta,
                                    void* costs, hipStream_t stream) __attribute__((weak));
+// SGPMP_COST_GRID_SDF (grid_sdf.hip): hinge value [batch] and gradient [batch, n] (entries >= 2 zero) of the term at the planar
+// point (q[0], q[1]); q laid out as launch_field_grad's (traj_T = 0: [B, n]; traj_T = T: waypoints 1 .. T-1 of [P, T, 2n]).
+// Weak for the same reason: sgpmp_field_grad and the GPMP linearisation refuse the kind where the definition is absent.
+hipError_t launch_grid_sdf_grad(int dtype, int n, const CostTerm& term, const void* q, long long batch, int traj_T, void* value,
+                                void* grad, hipStream_t stream) __attribute__((weak));
 hipError_t launch_link_dist(int dtype, const void* frames, long long batch, int n_links, const void* spheres,
                             int n_other, int mode, double buffer, void* out, hipStream_t stream);
 hipError_t launch_fk(int dtype, int n, const ChainDev* d_chain, int n_links, const void* q,

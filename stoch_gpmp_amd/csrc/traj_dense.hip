@@ -453,7 +453,7 @@ struct DenseCostK {
     int n_links;
     const real* spheres;              // DEVICE [n_spheres][4], or null
     int n_spheres;
-    int n_terms;                      // GRID / SPHERES / SELF terms of the cost program, in program order
+    int n_terms;                      // GRID / GRID_SDF / SPHERES / SELF terms of the cost program, in program order
     int has_qlim, has_vlim, accumulate;
     real weight, inv_sigma2;
     real q_lo[SGPMP_MAX_DOF], q_hi[SGPMP_MAX_DOF], v_max[SGPMP_MAX_DOF];
@@ -461,6 +461,20 @@ struct DenseCostK {
 };
 // (HIP passes at most 4 KiB of kernel arguments)
 static_assert(sizeof(DenseCostK<double>) + sizeof(HermiteK<double>) + 4 * sizeof(void*) <= 4096, "dense_cost_kernel: kernel arguments");
+
+// a term of the planar point itself: the occupancy lookup or the signed-distance grid's hinge
+template <typename real>
+__device__ __forceinline__ real planar_field(const TermK<real>& tm, real x, real y) {
+    return tm.kind == SGPMP_COST_GRID_SDF ? grid_sdf_field<real, false>(tm, x, y, nullptr, nullptr)
+                                          : grid_value<real>(tm, x, y);
+}
+
+// ... and the hinge with its derivative, for dense_cost_grad_kernel (a plain call there: the kernel's text is also compiled
+// without this header's functions, tests/test_cpu_dense_grad_wave.py, where the branch that calls it is never instantiated)
+template <typename real>
+__device__ __forceinline__ real grid_sdf_force(const TermK<real>& tm, real x, real y, real* fx, real* fy) {
+    return grid_sdf_field<real, true>(tm, x, y, fx, fy);
+}
 
 template <typename real, int N, int MODE>
 __global__ void __launch_bounds__(64)
@@ -540,7 +554,7 @@ dense_cost_kernel(const real* __restrict__ trajs, long long batch, DenseCostK<re
                         else if (tm.kind == SGPMP_COST_SELF)
                             f = self_field_cg<real, CC>(tm, Pq);
                         else
-                            f = grid_value<real>(tm, x[0], x[N > 1 ? 1 : 0]);
+                            f = planar_field<real>(tm, x[0], x[N > 1 ? 1 : 0]);
                         part += tm.K * f;
                     }
                 } else {
@@ -552,7 +566,7 @@ dense_cost_kernel(const real* __restrict__ trajs, long long batch, DenseCostK<re
                         fk_points_const<real, N>(as_const(A.chain), A.n_links, q, col);
                         for (int ti = 0; ti < A.n_terms; ++ti) {
                             const TermK<real>& tm = A.t[ti];
-                            if (tm.kind == SGPMP_COST_GRID) continue;
+                            if (tm.kind == SGPMP_COST_GRID || tm.kind == SGPMP_COST_GRID_SDF) continue;
                             if (tm.n_interp > 0) add_interp_points<real>(tm, A.n_links, col, 64);
                             const real f = tm.kind == SGPMP_COST_SPHERES
                                 ? spheres_field<real>(tm, tm.n_points, col, 64, A.spheres, A.n_spheres)
@@ -562,7 +576,8 @@ dense_cost_kernel(const real* __restrict__ trajs, long long batch, DenseCostK<re
                     }
                     for (int ti = 0; ti < A.n_terms; ++ti) {
                         const TermK<real>& tm = A.t[ti];
-                        if (tm.kind == SGPMP_COST_GRID) part += tm.K * grid_value<real>(tm, x[0], x[N > 1 ? 1 : 0]);
+                        if (tm.kind == SGPMP_COST_GRID || tm.kind == SGPMP_COST_GRID_SDF)
+                            part += tm.K * planar_field<real>(tm, x[0], x[N > 1 ? 1 : 0]);
                     }
                 }
             }
@@ -601,9 +616,10 @@ static hipError_t launch_dense_cost(const SgpmpCtxView& v, const void* trajs, lo
     for (int i = 0; v.prog && weight > 0. && n_sub > 0 && i < v.prog->n_terms; ++i) {
         const CostTerm& s = v.prog->terms[i];
         if (s.kind == SGPMP_COST_SPHERES && n_spheres < 1) continue;       // no obstacle: the term adds nothing
-        if (s.kind != SGPMP_COST_GRID && s.kind != SGPMP_COST_SPHERES && s.kind != SGPMP_COST_SELF) continue;
+        if (s.kind != SGPMP_COST_GRID && s.kind != SGPMP_COST_GRID_SDF && s.kind != SGPMP_COST_SPHERES && s.kind != SGPMP_COST_SELF)
+            continue;
         A.t[A.n_terms++] = make_termk<real>(s);
-        if (s.kind != SGPMP_COST_GRID) {
+        if (s.kind != SGPMP_COST_GRID && s.kind != SGPMP_COST_GRID_SDF) {
             fk = true;
             interp = interp || s.n_interp > 0;
             max_pts = s.n_points > max_pts ? s.n_points : max_pts;
@@ -962,7 +978,9 @@ __device__ __forceinline__ void joint_torques(ChainC chain, const S& s, real (&d
 
 static_assert(sizeof(DenseCostK<double>) + sizeof(HermiteK<double>) + 6 * sizeof(void*) <= 4096, "dense_cost_grad_kernel: kernel arguments");
 
-template <typename real, int N, int NJ>
+// SDF (NJ = -1 only): the terms are signed-distance grid terms (SGPMP_COST_GRID_SDF) -- a field of the planar point (x[0], x[1])
+// itself, its force goes onto entries 0 and 1 of the fine state; no kinematics, no LDS.
+template <typename real, int N, int NJ, bool SDF = false>
 __global__ void __launch_bounds__(64)
 dense_cost_grad_kernel(const real* __restrict__ trajs, long long batch, DenseCostK<real> A, HermiteK<real> H, int support,
                        real* __restrict__ grad, real* __restrict__ costs, double* __restrict__ costs64) {
@@ -1058,6 +1076,18 @@ dense_cost_grad_kernel(const real* __restrict__ trajs, long long batch, DenseCos
                         for (int k = 0; k < N; ++k) gq[k] += A.weight * dq[k];
                     }
                 }
+                if constexpr (SDF) {
+                    if (m > 0 || (support && i >= 1)) {        // the range of the link fields above
+                        for (int ti = 0; ti < A.n_terms; ++ti) {
+                            real fx, fy;
+                            const real h = grid_sdf_force(A.t[ti], x[0], x[N > 1 ? 1 : 0], &fx, &fy);
+                            const real w = A.weight * A.t[ti].K;
+                            part += A.t[ti].K * h;
+                            gq[0] += w * fx;
+                            gq[N > 1 ? 1 : 0] += w * fy;
+                        }
+                    }
+                }
                 if (m == 0) {                                  // the support state itself: the identity
 #pragma unroll
                     for (int k = 0; k < N; ++k) { ga[k] += gq[k]; ga[N + k] += gv[k]; }
@@ -1107,9 +1137,11 @@ static int launch_dense_cost_grad(const SgpmpCtxView& v, const void* trajs, long
     A.T = v.dims.traj_len; A.n_sub = n_sub; A.accumulate = accumulate ? 1 : 0;
     A.weight = (real)weight;
     bool interp = false;
+    int n_sdf = 0;
     // weight 0 (the limit part alone) evaluates no field; neither does n_sub 0 without the support waypoints
     for (int i = 0; v.prog && weight > 0. && (n_sub > 0 || support) && i < v.prog->n_terms; ++i) {
         const CostTerm& s = v.prog->terms[i];
+        if (s.kind == SGPMP_COST_GRID_SDF) { A.t[A.n_terms++] = make_termk<real>(s); ++n_sdf; continue; }
         if (s.kind != SGPMP_COST_SPHERES && s.kind != SGPMP_COST_SELF) continue;   // (a GRID term with n_sub > 0 was refused)
         if (s.kind == SGPMP_COST_SPHERES && n_spheres < 1) continue;               // no obstacle: the term adds nothing
         A.t[A.n_terms++] = make_termk<real>(s);
@@ -1129,7 +1161,11 @@ static int launch_dense_cost_grad(const SgpmpCtxView& v, const void* trajs, long
     const char* name = "";
     size_t lds = 0;
     int nj = -1;                                               // -1: no link field; 0: generic; 10, 7: compile-time chain length
-    if (A.n_terms > 0) {
+    if (n_sdf > 0 && n_sdf < A.n_terms)
+        return sgpmp_set_error(SGPMP_EINVAL, "sgpmp_dense_cost_grad: a grid distance term together with link-field terms is not "
+                                             "supported (the grid distance field belongs to planar cost lists)");
+    if (n_sdf > 0 && n < 2) return sgpmp_set_error(SGPMP_EINVAL, "sgpmp_dense_cost_grad: a grid distance term needs n_dof >= 2");
+    if (A.n_terms > 0 && n_sdf == 0) {
         A.spheres = n_spheres > 0 ? (const real*)spheres : nullptr;
         A.n_spheres = A.spheres ? n_spheres : 0;
         A.n_links = v.h_chain->n_links;
@@ -1164,6 +1200,18 @@ static int launch_dense_cost_grad(const SgpmpCtxView& v, const void* trajs, long
             GRAD_CASE(1, 0) GRAD_CASE(2, 0) GRAD_CASE(3, 0) GRAD_CASE(4, 0) GRAD_CASE(5, 0) GRAD_CASE(6, 0) GRAD_CASE(7, 0) GRAD_CASE(8, 0)
             default: return sgpmp_set_error(SGPMP_EINVAL, "sgpmp_dense_cost_grad: n_dof out of range");
         }
+    } else if (n_sdf > 0) {
+        name = f64 ? "dense_cost_grad_kernel<f64, grid distance>" : "dense_cost_grad_kernel<f32, grid distance>";
+#define GRAD_SDF_CASE(NN)                                                                                             \
+    case NN:                                                                                                          \
+        hipLaunchKernelGGL((dense_cost_grad_kernel<real, NN, -1, true>), grid, block, 0, stream, (const real*)trajs, \
+                           batch, A, H, support ? 1 : 0, (real*)grad, (real*)costs, costs64);                         \
+        break;
+        switch (n) {
+            GRAD_SDF_CASE(2) GRAD_SDF_CASE(3) GRAD_SDF_CASE(4) GRAD_SDF_CASE(5) GRAD_SDF_CASE(6) GRAD_SDF_CASE(7) GRAD_SDF_CASE(8)
+            default: return sgpmp_set_error(SGPMP_EINVAL, "sgpmp_dense_cost_grad: n_dof out of range");
+        }
+#undef GRAD_SDF_CASE
     } else {
         name = f64 ? "dense_cost_grad_kernel<f64, no FK>" : "dense_cost_grad_kernel<f32, no FK>";
         switch (n) {

@@ -550,6 +550,25 @@ class Engine:
                                               L.ptr(value), L.ptr(grad), L.stream_ptr()))
         return value, grad
 
+    def grid_sdf_build(self, occ, cell, threshold=0., out=None):
+        """Signed distance grid [ny, nx] of the occupancy grid occ [ny, nx] (device tensors of this engine's dtype): the exact
+        Euclidean distance transform in two launches on the current stream (include/sgpmp.h: sgpmp_grid_sdf_build; host-side
+        twin: stoch_gpmp_amd/grid_sdf.py).  `out`: a tensor to rebuild in place."""
+        self._chk(occ, "occ")
+        if occ.dim() != 2:
+            raise ValueError("grid_sdf_build: occ must be [ny, nx]")
+        ny, nx = int(occ.shape[0]), int(occ.shape[1])
+        if out is None:
+            out = torch.empty(ny, nx, **self.tensor_args)
+        else:
+            self._chk(out, "out")
+            if tuple(out.shape) != (ny, nx):
+                raise ValueError("grid_sdf_build: out must have occ's shape")
+        with torch.cuda.device(self.device):
+            L.check(self.lib.sgpmp_grid_sdf_build(self._ctx, L.ptr(occ) if occ.numel() else None, ny, nx, float(cell),
+                                                  float(threshold), L.ptr(out) if out.numel() else None, L.stream_ptr()))
+        return out
+
     # ------------------------------------------------------------------ dense trajectories
     def interpolate(self, trajs, n_sub, dt):
         """GP interpolation of trajs [B,T,d] with `n_sub` states inserted per interval -> [B,T_f,d], T_f = (T-1)(n_sub+1)+1

@@ -133,6 +133,104 @@ class ObstacleMap:
     def zero_grad(self):
         pass
 
+    def distance_field(self, margin, threshold=0.):
+        """The smooth collision field of this map: GridDistanceField(self, margin, threshold)."""
+        return GridDistanceField(self, margin, threshold=threshold)
+
+
+class GridDistanceField:
+    """Signed-distance grid of an ObstacleMap under the GPMP hinge, h = max(margin - d, 0) with d the bilinear interpolation of
+    the map's exact Euclidean signed distance (include/sgpmp.h: SGPMP_COST_GRID_SDF) -- the smooth field of a planar map scene:
+    CostCollision(field=...) accepts it in StochGPMP and, unlike the occupancy lookup, in GPMP, `continuous_cost` and
+    `get_linear_system`.  No reference counterpart.  The grid is built on the device (csrc/grid_sdf.hip); after editing the map
+    (`obst_map.map`, then `convert_map()`), `update()` rebuilds it."""
+    works_on_frames = False          # compute_cost takes points [..., 2]
+    needs_fk_chain = False           # FieldFactor: the Jacobian is with respect to the point itself
+
+    def __init__(self, obst_map, margin, threshold=0.):
+        if not margin >= 0.:
+            raise ValueError("GridDistanceField: margin must be >= 0")
+        self.obst_map = obst_map
+        self.margin = float(margin)
+        self.threshold = float(threshold)
+        self.tensor_args = obst_map.tensor_args
+        self._version = 0            # edit counter: planners re-compile their cost program when it moves
+        self._engines = {}
+        self._build_engine = None
+        self.sdf = None
+        self._build()
+
+    def _build(self):
+        om = self.obst_map
+        if om.map_torch is None:
+            om.convert_map()
+        L.require_cuda(self.tensor_args)
+        occ = om.map_torch
+        key = (occ.dtype, str(occ.device))
+        if self._build_engine is None or self._build_engine[0] != key:        # one context for every rebuild
+            self._build_engine = (key, Engine(2, 2, 0, 1, tensor_args={"device": occ.device, "dtype": occ.dtype}))
+        in_place = self.sdf is not None and self.sdf.shape == occ.shape and self.sdf.dtype == occ.dtype and \
+            self.sdf.device == occ.device
+        self.sdf = self._build_engine[1].grid_sdf_build(occ, om.cell_size, self.threshold, out=self.sdf if in_place else None)
+        if in_place:
+            # the query engines of the grid's own dtype point at this very tensor: still valid.  Those of another dtype hold a
+            # converted copy (Engine.set_costs), which is stale now
+            self._engines = {k: e for k, e in self._engines.items() if (k[1] if k[0] == "grad" else k[0]) == occ.dtype}
+        else:
+            self._engines = {}
+
+    def update(self):
+        """Rebuild the distance grid from the map's current `map_torch` (two launches, stream-ordered) and tell every planner
+        holding this field to re-compile its cost program before its next step."""
+        self._build()
+        self._version += 1
+        return self.sdf
+
+    def descriptor(self, sigma):
+        om = self.obst_map
+        return dict(kind=L.COST_GRID_SDF, sigma=sigma, sigma2=self.margin, device_tensor=self.sdf,
+                    dim0=self.sdf.shape[0], dim1=self.sdf.shape[1], p0=om.cell_size,
+                    p1=float(om.origin_xi), p2=float(om.origin_yi))
+
+    def _engine(self, dtype, device, distance=False):
+        key = (dtype, str(device), distance)
+        if key not in self._engines:
+            eng = Engine(2, 2, 0, 1, tensor_args={"device": device, "dtype": dtype})
+            eng.set_costs([dict(self.descriptor(1.0), flags=L.FLAG_GRID_DISTANCE if distance else 0)])
+            self._engines[key] = eng
+        return self._engines[key]
+
+    def compute_cost_and_grad(self, q, chain=None, **observations):
+        """Hinge value [B] and gradient [B, n] (entries >= 2 zero) at q [B, n], n >= 2: `grid_sdf_grad_kernel`."""
+        n = q.shape[-1]
+        key = ("grad", q.dtype, str(q.device), n)
+        if key not in self._engines:
+            eng = Engine(n, 2, 0, 1, tensor_args={"device": q.device, "dtype": q.dtype})
+            eng.set_costs([self.descriptor(1.0)])
+            self._engines[key] = eng
+        return self._engines[key].field_grad(0, q.reshape(-1, n).contiguous())
+
+    def compute_cost(self, X, **kwargs):
+        """X [..., 2] -> the hinge h."""
+        xy = X[..., :2].contiguous()
+        return self._engine(xy.dtype, xy.device).field_grad(0, xy.reshape(-1, 2))[0].reshape(X.shape[:-1])
+
+    def gradient(self, X):
+        """X [..., 2] -> dh / d(x, y) [..., 2]."""
+        xy = X[..., :2].contiguous()
+        return self._engine(xy.dtype, xy.device).field_grad(0, xy.reshape(-1, 2))[1].reshape(tuple(X.shape[:-1]) + (2,))
+
+    def compute_distance(self, X, **kwargs):
+        """X [..., 2] -> the interpolated signed distance d (negative inside obstacles)."""
+        xy = X[..., :2].contiguous()
+        return self._engine(xy.dtype, xy.device, distance=True).field_grad(0, xy.reshape(-1, 2))[0].reshape(X.shape[:-1])
+
+    def __call__(self, X, **kwargs):
+        return self.compute_cost(X, **kwargs)
+
+    def zero_grad(self):
+        pass
+
 
 def synthetic_obstacle_map(seed=0, map_dim=(20, 20), cell_size=0.1, num_obst=15,
                            rand_limits=((-7.5, 7.5), (-7.5, 7.5)), rect_shape=(2, 2),
