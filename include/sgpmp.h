@@ -61,8 +61,10 @@ enum {
     SGPMP_COST_SELF = 5,        /* CostCollision + LinkSelfDistanceField fields.py:114-124                 */
     SGPMP_COST_EE_GOAL = 6,     /* CostGoal + EESE3DistanceField         cost_functions.py:282-321, fields.py:130-153
                                    (SE3_distance itself is third-party and un-vendored: DESIGN.md)      */
-    SGPMP_COST_GRID_SDF = 7     /* CostCollision + GridDistanceField: hinge on a signed-distance grid (no reference
+    SGPMP_COST_GRID_SDF = 7,    /* CostCollision + GridDistanceField: hinge on a signed-distance grid (no reference
                                    counterpart; defined at sgpmp_grid_sdf_build below)                   */
+    SGPMP_COST_VOXEL_SDF = 8    /* CostCollision + VoxelDistanceField: hinge on a voxel signed-distance field at the link
+                                   points (no reference counterpart; defined at sgpmp_voxel_sdf_build below) */
 };
 enum { SGPMP_FIELD_RBF = 0, SGPMP_FIELD_SDF = 1, SGPMP_FIELD_OCCUPANCY = 2 };
 #define SGPMP_FLAG_GP_START 1      /* GP term includes the start-state unary factor (CostGP)  */
@@ -71,7 +73,8 @@ enum { SGPMP_FIELD_RBF = 0, SGPMP_FIELD_SDF = 1, SGPMP_FIELD_OCCUPANCY = 2 };
 #define SGPMP_FLAG_GRID_DISTANCE 64 /* GRID_SDF: sgpmp_field_grad returns the interpolated distance d and dd/d(x, y) instead of
                                       the hinge and its gradient (GridDistanceField.compute_distance).  A query flag, not a cost:
                                       allowed only in a cost list whose single term is this one (else SGPMP_EINVAL), and the
-                                      GPMP linearisation refuses a term that carries it */
+                                      GPMP linearisation refuses a term that carries it.  VOXEL_SDF: the same query, min over
+                                      the link points of d and the gradient through the first arg-min point */
 
 #define SGPMP_MAX_TERMS 8
 #define SGPMP_MAX_JOINTS 16
@@ -95,21 +98,23 @@ typedef struct sgpmp_dims {
 typedef struct sgpmp_cost_desc {
     int32_t kind;                  /* SGPMP_COST_*                                                */
     int32_t flags;                 /* GP: SGPMP_FLAG_GP_START; SPHERES: SGPMP_FIELD_* | SGPMP_FLAG_SDF_CLAMP;
-                                      GRID_SDF: SGPMP_FLAG_GRID_DISTANCE                           */
+                                      GRID_SDF, VOXEL_SDF: SGPMP_FLAG_GRID_DISTANCE                */
     double sigma;                  /* GP: sigma_gp; GOAL_PRIOR: sigma_goal_prior; collision: sigma_coll */
-    double sigma2;                 /* GP: sigma_start; SELF: margin; GRID_SDF: margin (>= 0)      */
-    double dt;                     /* GP: time step                                               */
+    double sigma2;                 /* GP: sigma_start; SELF: margin; GRID_SDF, VOXEL_SDF: margin (>= 0) */
+    double dt;                     /* GP: time step; VOXEL_SDF: the z offset oz                   */
     const void* data;              /* GP: HOST double[d] start state; GOAL_PRIOR: HOST double[G*d]
                                       goal states; GRID: DEVICE grid [dim0,dim1] in ctx dtype;
                                       GRID_SDF: DEVICE sdf [dim0 = ny, dim1 = nx] in ctx dtype;
+                                      VOXEL_SDF: DEVICE sdf [reserved = nz, dim0 = ny, dim1 = nx] in ctx dtype;
                                       EE_GOAL: HOST double[16] target frame (row-major 4x4), with
                                       p0 = w_pos, p1 = w_rot                                      */
     int32_t dim0, dim1;            /* GOAL_PRIOR: G, nppg*S of the cost (cost_functions.py:379);
-                                      GRID, GRID_SDF: map.shape[0], map.shape[1]                  */
-    double p0, p1, p2;             /* GRID, GRID_SDF: cell_size, c_offset[0], c_offset[1] (obst_map.py:129-140) */
+                                      GRID, GRID_SDF: map.shape[0], map.shape[1]; VOXEL_SDF: ny, nx */
+    double p0, p1, p2;             /* GRID, GRID_SDF: cell_size, c_offset[0], c_offset[1] (obst_map.py:129-140);
+                                      VOXEL_SDF: cell, ox, oy                                     */
     int32_t num_interpolate;       /* fields.py:32,94                                             */
     int32_t interp_lo, interp_hi;  /* link_interpolate_range                                      */
-    int32_t reserved;
+    int32_t reserved;              /* VOXEL_SDF: nz (0 for every other kind)                      */
     double alpha[SGPMP_MAX_INTERP];/* interpolation weights torch.linspace(0,1,K+2)[1:K+1] (fields.py:69) */
 } sgpmp_cost_desc;
 
@@ -499,6 +504,43 @@ int sgpmp_field_grad(sgpmp_ctx* ctx, int term, const void* q, int64_t batch, con
  * a SGPMP_COST_GRID term. */
 int sgpmp_grid_sdf_build(sgpmp_ctx* ctx, const void* occ, int ny, int nx, double cell, double threshold, void* sdf,
                          void* stream);
+
+/* ---- voxel signed-distance field (SGPMP_COST_VOXEL_SDF) -----------------------------------------
+ * The 3-D counterpart of the grid field above, for arm scenes: an occupancy volume's exact Euclidean signed distance,
+ * interpolated trilinearly, under the GPMP hinge, summed over the link points of the FK chain.  No reference counterpart.
+ *
+ * sgpmp_voxel_sdf_build: occ [nz, ny, nx] (x fastest; DEVICE, ctx dtype; a cell is occupied when (double)occ > threshold) ->
+ * sdf [nz, ny, nx] (DEVICE, ctx dtype), the signed distance at cell centres in world units, by sgpmp_grid_sdf_build's
+ * convention: for a free cell D^2 = min over occupied cells of the squared distance between the index triples and
+ * sdf = (sqrt(D^2) - 0.5) * cell, for an occupied cell the same over the free cells, negated.  Exact: squared distances are
+ * integers (<= 3 * 511^2, exact in fp32), one correctly rounded square root in double, then the subtract, the multiply, the
+ * conversion to the ctx dtype.  No occupied cell: +cap everywhere; no free cell: -cap; cap = cell * (nx + ny + nz); never
+ * infinite.  1 <= nx, ny, nz <= 512, cell > 0, a threshold that is not NaN, non-null occ != sdf: else SGPMP_EINVAL before any
+ * launch.  Stream-ordered, three launches (along z, y, x), IN PLACE in sdf: no scratch volume, no allocation, no host copy
+ * (the y pass stages a [ny][32] tile, <= 64 KiB, the x pass a row in LDS).
+ *
+ * The term: sgpmp_cost_desc { kind = SGPMP_COST_VOXEL_SDF, data = sdf, reserved = nz, dim0 = ny, dim1 = nx, p0 = cell,
+ * p1 = ox, p2 = oy, dt = oz, sigma -> K = 1 / sigma^2, sigma2 = margin >= 0, num_interpolate / interp_lo / interp_hi / alpha as
+ * for SGPMP_COST_SPHERES }.  (dt and reserved are fields no other link field uses: the struct's layout does not move.)  The
+ * points p are those of SGPMP_COST_SPHERES: every link origin of the chain, then the interpolated points.  Per point
+ *   u = px * (1 / cell) + ox - 0.5, v = py * (1 / cell) + oy - 0.5, w = pz * (1 / cell) + oz - 0.5   (multiply, add: rounded separately)
+ *   i0 = floor(u), fx = u - i0; i0, i0 + 1 clamped to [0, nx - 1]; j0, fy from v and ny, k0, fz from w and nz likewise
+ *   s[k][j][i] = sdf[(k * ny + j) * nx + i];  trilinear, x first, then y, then z:
+ *   c_kj = (1 - fx) s[k][j][i0] + fx s[k][j][i1];  e_k = (1 - fy) c_k,j0 + fy c_k,j1;  d = (1 - fz) e_k0 + fz e_k1
+ *   dd/dx = ((1 - fz) ((1 - fy) (s[k0][j0][i1] - s[k0][j0][i0]) + fy (s[k0][j1][i1] - s[k0][j1][i0]))
+ *            + fz ((1 - fy) (s[k1][j0][i1] - s[k1][j0][i0]) + fy (s[k1][j1][i1] - s[k1][j1][i0]))) * (1 / cell)
+ *   dd/dy = ((1 - fz) (c_k0,j1 - c_k0,j0) + fz (c_k1,j1 - c_k1,j0)) * (1 / cell),  dd/dz = (e_k1 - e_k0) * (1 / cell)
+ *   h_p = margin - d where that is > 0, else 0;  dh_p/dp = -grad d where h_p > 0, exactly 0 elsewhere.
+ * A clamped axis (outside the volume) has a zero derivative; a non-finite coordinate gives NaN in the value and the gradient.
+ * The field is f(q) = sum over the points of h_p; in a cost list the term is K * sum over t = 1 .. T-1 of f(q_t).  It needs an
+ * FK chain (SGPMP_ESTATE without one).  Consumers: sgpmp_cost_eval / sgpmp_step (sampler + generic sweep + update: no fused
+ * launch takes it), sgpmp_field_eval on explicit frames, sgpmp_field_grad, and one of the four field slots of
+ * sgpmp_gpmp_linearize (with and without sgpmp_gpmp_set_dense).  With SGPMP_FLAG_GRID_DISTANCE sgpmp_field_grad returns
+ * min over the points of d and the gradient through the FIRST arg-min point (point order, strict comparison): a query, allowed
+ * only as the cost list's single term (else SGPMP_EINVAL) and refused by GPMP.  sgpmp_dense_cost, sgpmp_dense_cost_grad and
+ * sgpmp_validate refuse a cost list that holds the term (SGPMP_EINVAL): their kernels do not evaluate it. */
+int sgpmp_voxel_sdf_build(sgpmp_ctx* ctx, const void* occ, int nz, int ny, int nx, double cell, double threshold, void* sdf,
+                          void* stream);
 
 /* trajs [B,T,d] -> out [B,T_f,d], ctx dtype, T = dims.traj_len. */
 int sgpmp_interpolate(sgpmp_ctx* ctx, const void* trajs, int64_t batch, int n_sub, double dt, void* out, void* stream);

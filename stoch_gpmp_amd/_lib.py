@@ -14,6 +14,7 @@ SGPMP_F32, SGPMP_F64 = 0, 1
 PRIOR_INIT, PRIOR_SAMPLE = 0, 1
 COST_GP, COST_GOAL_PRIOR, COST_GRID, COST_SPHERES, COST_SELF, COST_EE_GOAL = 1, 2, 3, 4, 5, 6
 COST_GRID_SDF = 7                    # the hinge on a signed-distance grid (envs/obst_map.py: GridDistanceField)
+COST_VOXEL_SDF = 8                   # the hinge on a voxel signed-distance field (envs/voxel_map.py: VoxelDistanceField)
 FIELD_RBF, FIELD_SDF, FIELD_OCCUPANCY = 0, 1, 2
 FLAG_GP_START, FLAG_SDF_CLAMP, FLAG_EE_SQUARE, FLAG_GRID_DISTANCE = 1, 16, 32, 64
 MAX_TERMS, MAX_JOINTS, MAX_DOF, MAX_INTERP = 8, 16, 8, 8
@@ -104,6 +105,7 @@ SIGNATURES = {
     "sgpmp_link_distances": (_I, [_P, _P, _I64, _I, _P, _I, _I, _D, _P, _P]),
     "sgpmp_field_grad": (_I, [_P, _I, _P, _I64, _P, _I, _P, _P, _P]),
     "sgpmp_grid_sdf_build": (_I, [_P, _P, _I, _I, _D, _D, _P, _P]),
+    "sgpmp_voxel_sdf_build": (_I, [_P, _P, _I, _I, _I, _D, _D, _P, _P]),
     "sgpmp_interpolate": (_I, [_P, _P, _I64, _I, _D, _P, _P]),
     "sgpmp_validate": (_I, [_P, _P, _I64, _I, _D, _P, _I, _I, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), _P, _P, _P]),
     "sgpmp_dense_cost": (_I, [_P, _P, _I64, _I, _D, _P, _I, _D, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), _D, _I, _P, _P, _P]),

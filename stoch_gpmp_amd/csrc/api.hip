@@ -687,6 +687,29 @@ extern "C" int sgpmp_set_costs(sgpmp_ctx* c, const sgpmp_cost_desc* descs, int n
                 t.off_x = s.p1; t.off_y = s.p2;
                 t.K2 = s.sigma2;                                  // the hinge's margin (TermK::K2)
                 break;
+            case SGPMP_COST_VOXEL_SDF:
+                // packing (include/sgpmp.h): reserved = nz, dim0 = ny, dim1 = nx, p0 = cell, p1 / p2 / dt = the offsets, sigma2 = margin
+                if (!s.data || s.reserved < 1 || s.dim0 < 1 || s.dim1 < 1 || !(s.p0 > 0.) || !(s.sigma2 >= 0.))
+                    return fail(SGPMP_EINVAL, "sgpmp_set_costs: voxel distance term needs a device sdf volume, cell size and margin >= 0");
+                if (c->dims.n_dof < 1)
+                    return fail(SGPMP_EINVAL, "sgpmp_set_costs: voxel distance term needs n_dof >= 1");
+                if ((s.flags & SGPMP_FLAG_GRID_DISTANCE) && n_desc != 1)
+                    return fail(SGPMP_EINVAL, "sgpmp_set_costs: SGPMP_FLAG_GRID_DISTANCE is a query flag for sgpmp_field_grad: "
+                                              "the term must be the cost list's only one");
+                if (s.num_interpolate < 0 || s.num_interpolate > SGPMP_MAX_INTERP)
+                    return fail(SGPMP_EINVAL, "sgpmp_set_costs: num_interpolate must be in [0, 8]");
+                t.n_interp = s.num_interpolate;
+                t.interp_lo = s.interp_lo; t.interp_hi = s.interp_hi;
+                for (int a = 0; a < s.num_interpolate; ++a) t.alpha[a] = s.alpha[a];
+                t.dev_data = s.data;
+                t.dim0 = s.dim0; t.dim1 = s.dim1;
+                t.rows_per_goal = s.reserved;                     // nz (TermK::rows_per_goal)
+                t.inv_cell = 1. / s.p0;
+                t.off_x = s.p1; t.off_y = s.p2;
+                t.dt = s.dt;                                      // the z offset (TermK::dt)
+                t.K2 = s.sigma2;                                  // the hinge's margin (TermK::K2)
+                prog.needs_fk = 1;
+                break;
             case SGPMP_COST_SPHERES:
             case SGPMP_COST_SELF:
                 if (s.num_interpolate < 0 || s.num_interpolate > SGPMP_MAX_INTERP)
@@ -937,7 +960,7 @@ static int finalize_program(sgpmp_ctx* c) {
         return fail(SGPMP_ESTATE, "link-distance / end-effector cost terms need an FK chain (sgpmp_set_fk)");
     for (int i = 0; i < p.n_terms; ++i) {
         CostTerm& t = p.terms[i];
-        if (t.kind != SGPMP_COST_SPHERES && t.kind != SGPMP_COST_SELF) continue;
+        if (t.kind != SGPMP_COST_SPHERES && t.kind != SGPMP_COST_SELF && t.kind != SGPMP_COST_VOXEL_SDF) continue;
         const int L = c->h_chain.n_links;
         int extra = 0;
         if (t.n_interp > 0) {
@@ -1526,7 +1549,8 @@ extern "C" int sgpmp_field_eval(sgpmp_ctx* c, int term, const void* frames, int6
     if (!c->have_costs || term < 0 || term >= c->h_prog.n_terms)
         return fail(SGPMP_EINVAL, "sgpmp_field_eval: bad term index");
     CostTerm t = c->h_prog.terms[term];
-    if (t.kind != SGPMP_COST_SPHERES && t.kind != SGPMP_COST_SELF && t.kind != SGPMP_COST_EE_GOAL)
+    if (t.kind != SGPMP_COST_SPHERES && t.kind != SGPMP_COST_SELF && t.kind != SGPMP_COST_EE_GOAL &&
+        t.kind != SGPMP_COST_VOXEL_SDF)
         return fail(SGPMP_EINVAL, "sgpmp_field_eval: term is not a link field");
     if (t.kind == SGPMP_COST_SPHERES && (!spheres || n_spheres < 1))
         return fail(SGPMP_EINVAL, "LinkDistanceField cost needs obstacle_spheres");
@@ -1564,6 +1588,8 @@ extern "C" int sgpmp_field_grad(sgpmp_ctx* c, int term, const void* q, int64_t b
                                     (hipStream_t)stream));
         return SGPMP_OK;
     }
+    if (c->h_prog.terms[term].kind == SGPMP_COST_VOXEL_SDF && !c->have_chain)
+        return fail(SGPMP_ESTATE, "sgpmp_field_grad: the voxel distance term needs an FK chain (sgpmp_set_fk)");
     if (!c->have_chain) return fail(SGPMP_EINVAL, "sgpmp_field_grad: no FK chain (sgpmp_set_fk)");
     int rc;
     if ((rc = finalize_program(c)) != SGPMP_OK) return rc;
@@ -1576,7 +1602,7 @@ extern "C" int sgpmp_field_grad(sgpmp_ctx* c, int term, const void* q, int64_t b
         HIPCHK(launch_ee_grad(c->dims.dtype, c->dims.n_dof, t, c->d_chain, q, batch, 0, 1, 0, value, grad,
                               (hipStream_t)stream));
         return SGPMP_OK;
-    } else if (t.kind != SGPMP_COST_SELF) {
+    } else if (t.kind != SGPMP_COST_SELF && t.kind != SGPMP_COST_VOXEL_SDF) {
         return fail(SGPMP_EINVAL, "sgpmp_field_grad: term is not a smooth link field");
     }
     if (t.n_points > SGPMP_MAX_POINTS) return fail(SGPMP_EINVAL, "too many link points (max 32)");
@@ -1612,9 +1638,12 @@ static int gpmp_args(sgpmp_ctx* c, GpmpArgs& a, int* field_terms) {
                 /* fall through */
             case SGPMP_COST_EE_GOAL:                      // (a field row on the last waypoint only)
             case SGPMP_COST_SELF:
+            case SGPMP_COST_VOXEL_SDF:                    // (a link field like SPHERES: launch_field_grad)
             case SGPMP_COST_GRID_SDF:                     // (a field of the planar point: no FK chain)
                 if (t.kind == SGPMP_COST_GRID_SDF && (t.flags & SGPMP_FLAG_GRID_DISTANCE))
                     return fail(SGPMP_EINVAL, "GPMP: a grid distance term with SGPMP_FLAG_GRID_DISTANCE is a query, not a cost");
+                if (t.kind == SGPMP_COST_VOXEL_SDF && (t.flags & SGPMP_FLAG_GRID_DISTANCE))
+                    return fail(SGPMP_EINVAL, "GPMP: a voxel distance term with SGPMP_FLAG_GRID_DISTANCE is a query, not a cost");
                 if (a.n_fields == 4) return fail(SGPMP_EINVAL, "GPMP: more than 4 link-field terms");
                 field_terms[a.n_fields] = i;
                 a.f[a.n_fields].K = t.K;

@@ -161,6 +161,58 @@ __device__ __forceinline__ real grid_value(const TermK<real>& tm, real x, real y
     return grid[(size_t)iy * tm.dim1 + ix];
 }
 
+// ---------------------------------------------------------------------------------- voxel signed-distance field
+// SGPMP_COST_VOXEL_SDF (include/sgpmp.h has the definition).  voxel_sdf_distance: the trilinear interpolation d between the cell
+// centres of the volume tm.dev_data [nz = rows_per_goal][ny = dim0][nx = dim1] (x fastest), clamp-to-edge, x first, then y, then
+// z; with GRAD also dd/d(x, y, z) into dd[3].  The z offset travels in tm.dt, nz in tm.rows_per_goal: two fields no link field
+// uses, so no kernel-argument struct changes.  A clamped axis reads the same cell twice, so its derivative is zero.  A non-finite
+// coordinate gives d = NaN: the index clamp may drop the NaN (fmin / fmax do), the fractions keep it.
+template <typename real, bool GRAD>
+__device__ __forceinline__ real voxel_sdf_distance(const TermK<real>& tm, real px, real py, real pz, real* dd) {
+    using O = RealOps<real>;
+    const real u = O::add_rn(O::mul_rn(px, tm.inv_cell), tm.off_x) - (real)0.5;
+    const real v = O::add_rn(O::mul_rn(py, tm.inv_cell), tm.off_y) - (real)0.5;
+    const real w = O::add_rn(O::mul_rn(pz, tm.inv_cell), tm.dt) - (real)0.5;
+    const real fu = O::floor_(u), fv = O::floor_(v), fw = O::floor_(w);
+    const real fx = u - fu, fy = v - fv, fz = w - fw;
+    const int nx = tm.dim1, ny = tm.dim0;
+    const real hx = (real)(nx - 1), hy = (real)(ny - 1), hz = (real)(tm.rows_per_goal - 1);
+    const int i0 = (int)fmin(fmax(fu, (real)0), hx), i1 = (int)fmin(fmax(fu + (real)1, (real)0), hx);   // clamp in float first
+    const int j0 = (int)fmin(fmax(fv, (real)0), hy), j1 = (int)fmin(fmax(fv + (real)1, (real)0), hy);
+    const int k0 = (int)fmin(fmax(fw, (real)0), hz), k1 = (int)fmin(fmax(fw + (real)1, (real)0), hz);
+    const real* sdf = (const real*)tm.dev_data;
+    const size_t r00 = ((size_t)k0 * ny + j0) * nx, r01 = ((size_t)k0 * ny + j1) * nx;      // rows [k][j]
+    const size_t r10 = ((size_t)k1 * ny + j0) * nx, r11 = ((size_t)k1 * ny + j1) * nx;
+    const real s000 = sdf[r00 + i0], s001 = sdf[r00 + i1], s010 = sdf[r01 + i0], s011 = sdf[r01 + i1];   // s[k][j][i]
+    const real s100 = sdf[r10 + i0], s101 = sdf[r10 + i1], s110 = sdf[r11 + i0], s111 = sdf[r11 + i1];
+    const real ax = (real)1 - fx, ay = (real)1 - fy, az = (real)1 - fz;
+    const real c00 = ax * s000 + fx * s001, c01 = ax * s010 + fx * s011;                    // c[k][j]: along x
+    const real c10 = ax * s100 + fx * s101, c11 = ax * s110 + fx * s111;
+    const real e0 = ay * c00 + fy * c01, e1 = ay * c10 + fy * c11;                          // e[k]: along y
+    if constexpr (GRAD) {
+        dd[0] = (az * (ay * (s001 - s000) + fy * (s011 - s010)) + fz * (ay * (s101 - s100) + fy * (s111 - s110))) * tm.inv_cell;
+        dd[1] = (az * (c01 - c00) + fz * (c11 - c10)) * tm.inv_cell;
+        dd[2] = (e1 - e0) * tm.inv_cell;
+    }
+    return az * e0 + fz * e1;
+}
+// voxel_sdf_field: the hinge h = margin - d of one point where positive, else 0, with GRAD also dh/d(x, y, z) into g[3] (exactly
+// zero where the hinge is inactive).  The one function every consumer of the term calls -- the sweep's three FK flavours,
+// field_eval_kernel, field_grad_kernel (sgpmp_field_grad and the GPMP rows).  (One definition and one operation order, not a
+// promise of equal bits across kernels: the compiler may contract a multiply and an add differently where it inlines this.)
+// Selects that keep a NaN: it reaches the value and all three derivatives.
+template <typename real, bool GRAD>
+__device__ __forceinline__ real voxel_sdf_field(const TermK<real>& tm, real px, real py, real pz, real* g) {
+    real dd[3] = {0, 0, 0};
+    const real e = tm.K2 - voxel_sdf_distance<real, GRAD>(tm, px, py, pz, dd);   // K2: the margin
+    const bool off = e <= (real)0;                         // (false for a NaN: it passes through)
+    if constexpr (GRAD) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r) g[r] = off ? (real)0 : (e == e ? -dd[r] : e);
+    }
+    return off ? (real)0 : e;
+}
+
 // ---------------------------------------------------------------------------------- signed-distance grid field
 // SGPMP_COST_GRID_SDF (include/sgpmp.h has the definition).  grid_sdf_distance: the bilinear interpolation d between the cell
 // centres of the signed-distance grid tm.dev_data [dim0 = ny][dim1 = nx], clamp-to-edge, with GRAD also dd/dx, dd/dy.  The
@@ -312,6 +364,16 @@ __device__ __forceinline__ real self_field(const TermK<real>& tm, int np, const 
     return acc;
 }
 
+// VoxelDistanceField.compute_cost: the hinge summed over the np points of this lane (SGPMP_COST_VOXEL_SDF).
+template <typename real>
+__device__ __forceinline__ real voxel_field(const TermK<real>& tm, int np, const real* col, int stride) {
+    real acc = 0;
+    for (int i = 0; i < np; ++i)
+        acc += voxel_sdf_field<real, false>(tm, col[(i * 3 + 0) * stride], col[(i * 3 + 1) * stride], col[(i * 3 + 2) * stride],
+                                            nullptr);
+    return acc;
+}
+
 // ---------------------------------------------------------------------------------- generated-chain path
 // FKMODE >= 1000: the chain has build-time generated code (chain_code_generated.h): FK is
 // straight-line code with the joint constants folded in, only the DISTINCT link positions exist,
@@ -374,6 +436,16 @@ __device__ __forceinline__ real self_field_cg(const TermK<real>& tm, const real 
         const real dx = Pq[i][0] - Pq[j][0], dy = Pq[i][1] - Pq[j][1], dz = Pq[i][2] - Pq[j][2];
         acc += (real)CC::pair_w(p) * O::exp2_((dx * dx + dy * dy + dz * dz) * k);
     }
+    return acc;
+}
+
+// the voxel field on the distinct link positions: coincident links count with their multiplicity (an identity of the sum)
+template <typename real, class CC>
+__device__ __forceinline__ real voxel_field_cg(const TermK<real>& tm, const real (&Pq)[CC::NREP][3]) {
+    real acc = 0;
+#pragma unroll
+    for (int l = 0; l < CC::NREP; ++l)
+        acc += (real)CC::mult(l) * voxel_sdf_field<real, false>(tm, Pq[l][0], Pq[l][1], Pq[l][2], nullptr);
     return acc;
 }
 
@@ -485,6 +557,20 @@ __device__ __forceinline__ real self_field_reg(const TermK<real>& tm, ChainC cha
                 acc += w * O::exp2_((dx * dx + dy * dy + dz * dz) * k);
             }
         }
+    }
+    return acc;
+}
+
+template <typename real, int NJ>
+__device__ __forceinline__ real voxel_field_reg(const TermK<real>& tm, ChainC chain, const real (&PX)[NJ + 1],
+                                                const real (&PY)[NJ + 1], const real (&PZ)[NJ + 1]) {
+    constexpr int NL = NJ + 1;
+    ChainC ch = opaque(chain);
+    real acc = 0;
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+        const real m = (real)ch->plan.mult[l];             // 0: the link sits on an earlier one, which counts for both
+        if (m != 0) acc += m * voxel_sdf_field<real, false>(tm, PX[l], PY[l], PZ[l], nullptr);
     }
     return acc;
 }

@@ -615,6 +615,7 @@ __global__ void field_eval_kernel(const TermK<real> tm, const real* __restrict__
     if (tm.n_interp > 0) add_interp_points<real>(tm, n_links, col, stride);
     real v;
     if (tm.kind == SGPMP_COST_SPHERES) v = spheres_field<real>(tm, tm.n_points, col, stride, sph, n_sph);
+    else if (tm.kind == SGPMP_COST_VOXEL_SDF) v = voxel_field<real>(tm, tm.n_points, col, stride);
     else v = self_field<real>(tm, tm.n_points, col, stride);
     if (b < batch) out[b] = v;
 }
@@ -789,6 +790,29 @@ field_grad_kernel(const ChainDev* __restrict__ ch, TermK<real> tm, int n, const 
                 const real w = -e * ir2;
                 G[l][0] += w * dx; G[l][1] += w * dy; G[l][2] += w * dz;
             }
+        }
+    } else if (tm.kind == SGPMP_COST_VOXEL_SDF) {
+        if (tm.flags & SGPMP_FLAG_GRID_DISTANCE) {
+            // the query: min over the points of the interpolated distance d and dd/dp on the FIRST arg-min point (point order,
+            // strict comparison); a NaN distance anywhere makes the value and the gradient NaN
+            real best = (real)__builtin_inff(), bad = 0;
+            int bl = 0;
+            real bg[3] = {0, 0, 0};
+#pragma unroll
+            for (int l = 0; l < npts; ++l) {
+                real dd[3];
+                const real d = voxel_sdf_distance<real, true>(tm, P[l][0], P[l][1], P[l][2], dd);
+                if (!(d == d)) bad = d;
+                if (d < best) { best = d; bl = l; bg[0] = dd[0]; bg[1] = dd[1]; bg[2] = dd[2]; }
+            }
+            const bool nan = !(bad == bad);
+            val = nan ? bad : best;
+#pragma unroll
+            for (int l = 0; l < npts; ++l)
+                if (l == bl) { G[l][0] = nan ? bad : bg[0]; G[l][1] = nan ? bad : bg[1]; G[l][2] = nan ? bad : bg[2]; }
+        } else {
+#pragma unroll
+            for (int l = 0; l < npts; ++l) val += voxel_sdf_field<real, true>(tm, P[l][0], P[l][1], P[l][2], G[l]);
         }
     } else {                                                 // SELF: the full L x L sum of fields.py:124
         // = diagonal (value 1 each, no gradient) + twice the strict lower triangle

@@ -532,6 +532,8 @@ __device__ __forceinline__ void cost_sweep_body(const CostArgs<real>& a, const P
                                                                       (real)stat[wave * SGPMP_MAX_TERMS + ti]);
                             else if (tm.kind == SGPMP_COST_SELF)
                                 f = self_field_cg<real, CC>(tm, Pq);
+                            else if (tm.kind == SGPMP_COST_VOXEL_SDF)
+                                f = voxel_field_cg<real, CC>(tm, Pq);
                             else
                                 continue;
                             if (inner) part += tm.K * f;
@@ -548,6 +550,8 @@ __device__ __forceinline__ void cost_sweep_body(const CostArgs<real>& a, const P
                             f = spheres_field_reg<real, FKMODE>(tm, chain, PX, PY, PZ, a.spheres, a.n_spheres);
                         else if (tm.kind == SGPMP_COST_SELF)
                             f = self_field_reg<real, FKMODE>(tm, chain, PX, PY, PZ);
+                        else if (tm.kind == SGPMP_COST_VOXEL_SDF)
+                            f = voxel_field_reg<real, FKMODE>(tm, chain, PX, PY, PZ);
                         else
                             continue;
                         if (inner) part += tm.K * f;
@@ -556,11 +560,13 @@ __device__ __forceinline__ void cost_sweep_body(const CostArgs<real>& a, const P
                     fk_points<real, N>(a.chain, q, col, stride);
                     for (int ti = 0; ti < P.n_terms; ++ti) {
                         const TermK<real>& tm = P.t[ti];
-                        if (tm.kind != SGPMP_COST_SPHERES && tm.kind != SGPMP_COST_SELF) continue;
+                        if (tm.kind != SGPMP_COST_SPHERES && tm.kind != SGPMP_COST_SELF && tm.kind != SGPMP_COST_VOXEL_SDF) continue;
                         if (tm.n_interp > 0) add_interp_points<real>(tm, a.n_links, col, stride);
                         real f;
                         if (tm.kind == SGPMP_COST_SPHERES)
                             f = spheres_field<real>(tm, tm.n_points, col, stride, a.spheres, a.n_spheres);
+                        else if (tm.kind == SGPMP_COST_VOXEL_SDF)
+                            f = voxel_field<real>(tm, tm.n_points, col, stride);
                         else
                             f = self_field<real>(tm, tm.n_points, col, stride);
                         if (inner) part += tm.K * f;

@@ -408,6 +408,19 @@ extern "C" int sgpmp_interpolate(sgpmp_ctx* c, const void* trajs, int64_t batch,
     return e == hipSuccess ? SGPMP_OK : dense_hip_error("sgpmp_interpolate", e);
 }
 
+// The dense-trajectory kernels do not evaluate SGPMP_COST_VOXEL_SDF: a cost list that holds the term is refused by name, never
+// evaluated without it (which would drop a collision term).  -> the message, or null.
+static const char* voxel_term_refusal(const char* who, const SgpmpCtxView& v) {
+    static thread_local char msg[200];
+    for (int i = 0; v.prog && i < v.prog->n_terms; ++i)
+        if (v.prog->terms[i].kind == SGPMP_COST_VOXEL_SDF) {
+            snprintf(msg, sizeof(msg), "%s: cost term %d (SGPMP_COST_VOXEL_SDF) is not evaluated on dense trajectories; "
+                                       "the voxel distance term counts at the support waypoints only", who, i);
+            return msg;
+        }
+    return nullptr;
+}
+
 extern "C" int sgpmp_validate(sgpmp_ctx* c, const void* trajs, int64_t batch, int n_sub, double dt, const void* spheres,
                               int n_spheres, int grid_term, const double* q_lo, const double* q_hi, const double* v_max,
                               void* values, int32_t* where, void* stream) {
@@ -425,6 +438,7 @@ extern "C" int sgpmp_validate(sgpmp_ctx* c, const void* trajs, int64_t batch, in
     } else if (grid_term != -1) {
         return sgpmp_set_error(SGPMP_EINVAL, "sgpmp_validate: grid_term is not a grid term");
     }
+    if (const char* refused = voxel_term_refusal("sgpmp_validate", v)) return sgpmp_set_error(SGPMP_EINVAL, refused);
     if (spheres && n_spheres > 0 && !v.have_chain)
         return sgpmp_set_error(SGPMP_ESTATE, "sgpmp_validate: obstacle spheres need an FK chain (sgpmp_set_fk)");
     if (batch == 0) return SGPMP_OK;
@@ -694,6 +708,7 @@ extern "C" int sgpmp_dense_cost(sgpmp_ctx* c, const void* trajs, int64_t batch, 
     SgpmpCtxView v;
     const int view_rc = sgpmp_ctx_view(c, &v);
     if (view_rc != SGPMP_OK) return view_rc;                   // (finalize_program said why)
+    if (const char* refused = voxel_term_refusal("sgpmp_dense_cost", v)) return sgpmp_set_error(SGPMP_EINVAL, refused);
     for (int i = 0; v.prog && i < v.prog->n_terms; ++i) {
         const int kind = v.prog->terms[i].kind;
         if ((kind == SGPMP_COST_SPHERES || kind == SGPMP_COST_SELF) && !v.have_chain)
@@ -1239,6 +1254,7 @@ extern "C" int sgpmp_dense_cost_grad(sgpmp_ctx* c, const void* trajs, int64_t ba
     SgpmpCtxView v;
     const int view_rc = sgpmp_ctx_view(c, &v);
     if (view_rc != SGPMP_OK) return view_rc;                   // (finalize_program said why)
+    if (const char* refused = voxel_term_refusal("sgpmp_dense_cost_grad", v)) return sgpmp_set_error(SGPMP_EINVAL, refused);
     for (int i = 0; v.prog && i < v.prog->n_terms; ++i) {
         const int kind = v.prog->terms[i].kind;
         if ((kind == SGPMP_COST_SPHERES || kind == SGPMP_COST_SELF) && !v.have_chain)

@@ -304,6 +304,7 @@ class Engine:
             cd.p0, cd.p1, cd.p2 = (float(dsc.get(k, 0.0)) for k in ("p0", "p1", "p2"))
             cd.num_interpolate = int(dsc.get("num_interpolate", 0))
             cd.interp_lo, cd.interp_hi = int(dsc.get("interp_lo", 0)), int(dsc.get("interp_hi", 0))
+            cd.reserved = int(dsc.get("reserved", 0))                 # COST_VOXEL_SDF: nz
             for a, v in enumerate(dsc.get("alpha", [])):
                 cd.alpha[a] = float(v)
             if "host_data" in dsc:
@@ -567,6 +568,25 @@ class Engine:
         with torch.cuda.device(self.device):
             L.check(self.lib.sgpmp_grid_sdf_build(self._ctx, L.ptr(occ) if occ.numel() else None, ny, nx, float(cell),
                                                   float(threshold), L.ptr(out) if out.numel() else None, L.stream_ptr()))
+        return out
+
+    def voxel_sdf_build(self, occ, cell, threshold=0., out=None):
+        """Signed distance volume [nz, ny, nx] of the occupancy volume occ [nz, ny, nx] (device tensors of this engine's dtype):
+        the exact Euclidean distance transform in three launches on the current stream, in place in the output (include/sgpmp.h:
+        sgpmp_voxel_sdf_build; host-side twin: stoch_gpmp_amd/voxel_sdf.py).  `out`: a tensor to rebuild in place."""
+        self._chk(occ, "occ")
+        if occ.dim() != 3:
+            raise ValueError("voxel_sdf_build: occ must be [nz, ny, nx]")
+        nz, ny, nx = (int(v) for v in occ.shape)
+        if out is None:
+            out = torch.empty(nz, ny, nx, **self.tensor_args)
+        else:
+            self._chk(out, "out")
+            if tuple(out.shape) != (nz, ny, nx):
+                raise ValueError("voxel_sdf_build: out must have occ's shape")
+        with torch.cuda.device(self.device):
+            L.check(self.lib.sgpmp_voxel_sdf_build(self._ctx, L.ptr(occ) if occ.numel() else None, nz, ny, nx, float(cell),
+                                                   float(threshold), L.ptr(out) if out.numel() else None, L.stream_ptr()))
         return out
 
     # ------------------------------------------------------------------ dense trajectories
