@@ -168,6 +168,11 @@ void sgpmp_destroy(sgpmp_ctx* ctx);
  * the GP / goal-prior / importance-sampling terms stay fp64.  The collision part of a cost then carries fp32's ~1e-6 relative
  * error -- ~1e-9 of a total cost at the reference's hyper-parameters -- and the step runs 1.7 x as fast: 0.46 against 0.79 ms at BASELINE configs[2]'s shape; the occupancy COUNT is then taken on
  * fp32 link positions too: a point within fp32 rounding of a sphere's surface may count differently, one quantum 1 / sigma_coll^2),
+ * update_wide (1: update launches take update_kernel, one 256-thread workgroup per particle, even where update_kernel_quad -- one
+ * wave per particle, four particles per workgroup; the default for the halves of a two-chain step that store their samples, have
+ * no folded end-effector term, 512 to 1023 particles and at most 256 samples per particle, where it measured faster -- applies;
+ * -1: update_kernel_quad wherever it can run; 0: the rule.  Bit-identical.  PROCESS-WIDE, unlike every other switch: it holds for
+ * all contexts of the process; SGPMP_UPDATE_WIDE is read once per process, by the first sgpmp_create),
  * pipe_split (1..15) and k3_blocks (count).  (The launches that measured slower -- tail_update, small_step, planar_slabs,
  * wave_groups, fused_pipe -- were removed in round 5; DESIGN.md 8 keeps their numbers and the commit that last held them.)
  * No reference counterpart. */

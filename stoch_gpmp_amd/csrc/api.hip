@@ -134,6 +134,11 @@ static void toggles_from_env(SgpmpToggles& tg) {
     if (const char* e = getenv("SGPMP_STORE_FREE_MIN_BYTES")) tg.store_free_min_bytes = atoll(e);
     if (const char* e = getenv("SGPMP_SMALL_STEP_ITEMS")) tg.small_step_items = atoll(e);
     if (const char* e = getenv("SGPMP_PERSIST_MAX_ITERS")) tg.persist_max_iters = atoll(e);
+    static bool update_wide_read = false;                // (process-wide, sgpmp_internal.h: a later context does not change what a live one launches)
+    if (!update_wide_read) {
+        update_wide_read = true;
+        if (const char* e = getenv("SGPMP_UPDATE_WIDE")) { const long long v = atoll(e); g_sgpmp_update_wide = v > 0 ? 1 : v < 0 ? -1 : 0; }
+    }
 }
 
 #ifdef SGPMP_HOST_TIMING      // diagnostic build (tools/host_step_cost.py): host nanoseconds of sgpmp_step's segments, printed by sgpmp_destroy
@@ -232,6 +237,7 @@ extern "C" int sgpmp_set_option(sgpmp_ctx* c, const char* name, long long value)
     if (std::strcmp(name, "store_free_min_bytes") == 0) { c->tg.store_free_min_bytes = value; return SGPMP_OK; }
     if (std::strcmp(name, "small_step_items") == 0) { c->tg.small_step_items = value; return SGPMP_OK; }
     if (std::strcmp(name, "persist_max_iters") == 0) { c->tg.persist_max_iters = value; return SGPMP_OK; }
+    if (std::strcmp(name, "update_wide") == 0) { g_sgpmp_update_wide = value > 0 ? 1 : value < 0 ? -1 : 0; return SGPMP_OK; }   // (process-wide: sgpmp_internal.h)
     for (const auto& t : kToggleNames)
         if (std::strcmp(name, t.name) == 0) { c->tg.*(t.flag) = value != 0; return SGPMP_OK; }
     return fail(SGPMP_EINVAL, std::string("sgpmp_set_option: unknown option ") + name);
@@ -1308,7 +1314,7 @@ static int run_range(sgpmp_ctx* c, const StepPlan& plan, const StepArgs& a, size
         HIPCHK(launch_update(D.dtype, D.n_dof, D.traj_len, P, S, c64, SGPMP_F64, X, mu, a.temperature, a.step_size, wh, gh, mph,
                              slot, st, c->tg.comm_packet_event ? k4_done : nullptr, &pr, isw, isw_written, means_copy,
                              plan.partials ? io.dense.part : nullptr, io.dense.nnz, dense.threshold,
-                             regen.recipe != 0 ? &regen : nullptr, eet ? &eeh : nullptr));
+                             &regen, eet ? &eeh : nullptr));        // (recipe 0: nothing to regenerate; beside_chain all the same)
         if (!c->tg.comm_packet_event && k4_done) HIPCHK(hipEventRecord(k4_done, st));
         launches += 1;
     }

@@ -244,7 +244,21 @@ struct RegenHost {
     const float* coef;            // recipe 1: PriorDev::iso32p; 2: PriorDev::iso32
     const float* pre;             // recipe 2: the segment table of PriorDev::slabpre
     unsigned store_threshold;
+    int beside_chain;             // the launch is one half of a two-chain step: it runs beside the other half's fused launch (which update
+                                  // kernel launch_update takes; set with recipe 0 too)
 };
+// update_kernel_quad (update.hip): particles per workgroup, one wave each; the most samples and the range of particles of a
+// half's launch that takes it by default (update.hip: update_quad_applies has the measurements)
+#define SGPMP_UPD_QUAD 4
+#define SGPMP_UPD_QUAD_MAX_S 256
+#define SGPMP_UPD_QUAD_MIN_P 512
+#define SGPMP_UPD_QUAD_END_P 1024
+// Development switch `update_wide` (sgpmp_set_option / SGPMP_UPDATE_WIDE): > 0: every update launch takes update_kernel (one
+// 256-thread workgroup per particle); < 0: update_kernel_quad wherever it can run, also where it is not the faster one; 0: the
+// measured rule.  PROCESS-WIDE, unlike the switches of SgpmpToggles: launch_update is handed no toggles, so the value lives here
+// (one variable for the whole library: C++17 inline).  SGPMP_UPDATE_WIDE is read ONCE per process, by the first sgpmp_create;
+// after that only sgpmp_set_option changes it, for every context of the process.
+inline int g_sgpmp_update_wide = 0;
 int update_regen_rows(int dtype, int n, int T, int S, int recipe);   // rows per round update_kernel can regenerate; 0: not this shape
 bool update_ee_fold_fits(int dtype, int n, int T, int S);
 
@@ -292,6 +306,7 @@ StepPlan plan_step(const StepShape& shape, const StepWants& wants, const PriorDe
 // what update_kernel is told behind a launch of this plan (recipe 0: nothing to regenerate)
 static inline RegenHost plan_regen(const StepPlan& plan, const PriorDev& prior, uint64_t seed, uint64_t draw, unsigned store_threshold) {
     RegenHost r = {};
+    r.beside_chain = plan.shape.P < plan.shape.particles_total;   // (a half of a two-chain step: api.hip, plan_two_chains)
     if (plan.regen_recipe == 0) return r;
     r.recipe = plan.regen_recipe; r.L = r.recipe == 2 ? plan.L : 0; r.seed = seed; r.draw = draw; r.mode_offset = plan.shape.offset;
     r.coef = r.recipe == 1 ? prior.iso32p : prior.iso32;

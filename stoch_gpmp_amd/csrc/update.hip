@@ -42,6 +42,71 @@ bool update_ee_fold_fits(int dtype, int n, int T, int S) {
     return ((update_base_lds(dtype, n, T, S) + 15) & ~(size_t)15) + (size_t)S * sizeof(double) + 256 <= 65536;
 }
 
+// update_kernel with ONE WAVE per particle: wave w of workgroup b updates particle 4 b + w in its own slice of the dynamic
+// LDS (update_particle<.., 64>: no workgroup barrier, the four particles do not wait for each other), then ONE barrier and one
+// importance-sampling tail for the four particles with all 256 threads (is_weight_elem of the owning particle's means in
+// LDS: a pure function of (means, e), the bits of update_kernel's tail).  A quarter of update_kernel's waves: inside a
+// two-chain optimize() the update runs under the other chain's fused launch, where every wave waits for a slot, and its
+// duration there is serial in its own chain -- 55.9 -> 45.9 us per half at the headline shape (profiles/r12).
+// Storing steps without a folded end-effector term only (launch_update).
+template <typename real, typename cost_t, int VW>
+__global__ void __launch_bounds__(256)
+update_kernel_quad(int M, int S, int P, const cost_t* __restrict__ costs, const real* __restrict__ samples,
+                   real* __restrict__ means, double temperature, double step_size,
+                   real* __restrict__ weights, real* __restrict__ grad, real* __restrict__ means_prev,
+                   double* __restrict__ stats, IswNext<real> nx, real* __restrict__ means_copy,
+                   const float* __restrict__ part, int gpp, unsigned* __restrict__ nnz, unsigned nnz_threshold,
+                   unsigned slice_bytes) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int p0 = (int)blockIdx.x * SGPMP_UPD_QUAD, p = p0 + wave;
+    // (issued first, consumed last -- as in update_particle's own tail)
+    const bool iso_tail = nx.out && nx.isotropic;
+    const int nd = 2 * nx.n;
+    const double q00 = iso_tail ? nx.Qinv[0] : 0., q01 = iso_tail ? nx.Qinv[nx.n] : 0.;
+    const double q10 = iso_tail ? nx.Qinv[nx.n * nd] : 0., q11 = iso_tail ? nx.Qinv[nx.n * nd + nx.n] : 0.;
+    if (p < P) {                                         // (a wave without a particle goes straight to the barrier)
+        const unsigned prev = nnz ? nnz[p] : 0u;         // partials exist iff THIS step's launch saw the count above the threshold
+        const float* part_p = nullptr;
+        if (part && nnz && prev > nnz_threshold) part_p = part + (size_t)p * gpp * (M + 4);
+        update_particle<real, cost_t, VW, 64>(p, M, S, costs + (size_t)p * S, samples + (size_t)p * S * M, (size_t)M, means,
+                                              temperature, step_size, weights, grad, means_prev, stats, nx, means_copy,
+                                              lds_raw + (size_t)wave * slice_bytes, nullptr, part_p, gpp, nnz ? nnz + p : nullptr);
+    }
+    if (nx.out) {
+        __syncthreads();                                  // the new means of the workgroup's particles are in their slices
+        const int Tn = M / nd, E = (Tn + 1) * nd;         // elements per particle; particle p0 + q owns [q E, (q + 1) E)
+        const int live = P - p0 < SGPMP_UPD_QUAD ? P - p0 : SGPMP_UPD_QUAD;
+        const size_t mu_off = ((size_t)S * 12 + 15) & ~(size_t)15;
+        real* out = nx.out + (size_t)p0 * E;
+        for (int i = threadIdx.x; i < live * E; i += SGPMP_UPD_THREADS) {
+            const int q = i / E, e = i - q * E;
+            const real* mu_new = reinterpret_cast<const real*>(lds_raw + (size_t)q * slice_bytes + mu_off);
+            out[i] = iso_tail ? is_weight_elem_iso<real>(nx.n, Tn, mu_new, q00, q01, q10, q11, nx.ks, nx.kg, nx.dt, temperature, e)
+                              : is_weight_elem<real>(nx.n, Tn, mu_new, nx.Qinv, nx.ks, nx.kg, nx.dt, temperature, nx.isotropic, e);
+        }
+    }
+}
+
+// Which launches take update_kernel_quad: a function of (S, P), the scratch size and what the launch is asked for, never of
+// timing.  It can run wherever nothing is regenerated, no end-effector term is folded in and four slices fit the workgroup's
+// LDS (the switch update_wide < 0 takes it there: tests, A/B).  It is TAKEN where it measured faster
+// (profiles/r12/update_quad_ab.txt and update_quad_rule_points.txt, same machine, alternating runs):
+//  * only for a half of a two-chain step (RegenHost::beside_chain).  Alone on the GPU it is the longer kernel -- a lane owns
+//    S / 64 costs and as many of the virtual waves' butterflies, one after the other: config 2 (planar 256 x 64 x 128, one
+//    chain) lost 10 .. 13 %, config 1 (planar 4 x 16 x 64 fp64) 3 .. 8 %, single-iteration calls at the headline shape
+//    (P = 1024, one chain) 1.0 .. 2.6 % with it.
+//  * SGPMP_UPD_QUAD_MIN_P = 512 <= P < SGPMP_UPD_QUAD_END_P = 1024 particles per half.  Against update_kernel, Panda T = 64,
+//    whole problem P x S: 1024 x 128 (the headline) +2.4 .. +3.2 %, 1024 x 64 +0.4 .. +3.2 %, 1024 x 256 +0.6 .. +1.6 %;
+//    512 x 128 (halves of 256) level inside 2 % of noise, config 5's share (512 x 256, T = 128) -1.3 .. -3.5 %;
+//    2048 x 128 (halves of 1024) -0.6, -0.9, +0.2 %.
+//  * S <= SGPMP_UPD_QUAD_MAX_S = 256, where the measurements end (+0.6 .. +1.6 % at 1024 x 256: four costs per lane).
+static bool update_quad_applies(int S, int P, size_t lds_one, bool regen, bool ee, bool beside_chain) {
+    if (g_sgpmp_update_wide > 0 || regen || ee) return false;
+    if (SGPMP_UPD_QUAD * ((lds_one + 15) & ~(size_t)15) + 256 > 65536) return false;
+    return g_sgpmp_update_wide < 0 || (beside_chain && S <= SGPMP_UPD_QUAD_MAX_S && P >= SGPMP_UPD_QUAD_MIN_P && P < SGPMP_UPD_QUAD_END_P);
+}
+
 hipError_t launch_update(int dtype, int n, int T, int P, int S, const void* costs, int costs_dtype,
                          const void* samples, void* means, double temperature, double step_size,
                          void* weights, void* grad, void* means_prev, double* stats,
@@ -59,6 +124,7 @@ hipError_t launch_update(int dtype, int n, int T, int P, int S, const void* cost
         if (with_tail + 256 <= 65536) lds = with_tail;
         else isw_prior = nullptr;
     }
+    const bool tail_fits = isw_prior != nullptr || isw_next == nullptr;
     if (isw_written) *isw_written = isw_prior != nullptr && P > 0;
     if (P <= 0) return hipSuccess;
     // store-free step: the rows with weight are regenerated behind the kernel's usual scratch
@@ -84,6 +150,12 @@ hipError_t launch_update(int dtype, int n, int T, int P, int S, const void* cost
         if (lds + 256 > 65536) return hipErrorInvalidValue;      // (the caller checks update_ee_fold_fits first)
     }
     dim3 grid(P), block(256);
+    const bool quad = tail_fits && update_quad_applies(S, P, lds, rg.recipe != 0, ee && ee->term, regen && regen->beside_chain);
+    const unsigned slice = (unsigned)((lds + 15) & ~(size_t)15);
+    if (quad) {
+        grid = dim3((P + SGPMP_UPD_QUAD - 1) / SGPMP_UPD_QUAD);
+        lds = (size_t)SGPMP_UPD_QUAD * slice;
+    }
     // `done` (multi-GPU statistics): the event is signalled by this kernel's own dispatch packet
     // (hipExtLaunchKernelGGL stop event) instead of a separate barrier packet behind it
 #define UPD(REAL, COST, VW)                                                                          \
@@ -95,7 +167,23 @@ hipError_t launch_update(int dtype, int n, int T, int P, int S, const void* cost
                                         isw_prior ? isw_prior->dt : 0., n, isw_prior ? isw_prior->isotropic : 1}, \
                           (REAL*)means_copy, (dtype == SGPMP_F32 && M % 4 == 0) ? part : (const float*)nullptr, (S + 7) / 8, nnz, nnz_threshold, rg, regen_off, \
                           (ee && ee->term) ? EeFold<REAL>{ee->d_chain, make_ee_target<REAL>(*ee->term), n, T, (REAL*)ee->costs} : EeFold<REAL>{nullptr, EeTarget<REAL>{}, n, T, nullptr}, ee_off)
-    if (dtype == SGPMP_F64) {
+#define UPDQ(REAL, COST, VW)                                                                         \
+    hipExtLaunchKernelGGL((update_kernel_quad<REAL, COST, VW>), grid, block, (unsigned)lds, stream, (hipEvent_t) nullptr, \
+                          done, 0u, M, S, P, (const COST*)costs, (const REAL*)samples, (REAL*)means, temperature, \
+                          step_size, (REAL*)weights, (REAL*)grad, (REAL*)means_prev, stats,          \
+                          IswNext<REAL>{isw_prior ? (REAL*)isw_next : nullptr, isw_prior ? isw_prior->Qinv : nullptr, \
+                                        isw_prior ? isw_prior->ks : 0., isw_prior ? isw_prior->kg : -1., \
+                                        isw_prior ? isw_prior->dt : 0., n, isw_prior ? isw_prior->isotropic : 1}, \
+                          (REAL*)means_copy, (dtype == SGPMP_F32 && M % 4 == 0) ? part : (const float*)nullptr, (S + 7) / 8, nnz, nnz_threshold, slice)
+    if (quad) {
+        if (dtype == SGPMP_F64) {
+            if (M % 4 == 0) UPDQ(double, double, 4); else UPDQ(double, double, 2);
+        } else if (costs_dtype == SGPMP_F64) {
+            if (M % 4 == 0) UPDQ(float, double, 4); else UPDQ(float, double, 2);
+        } else {
+            if (M % 4 == 0) UPDQ(float, float, 4); else UPDQ(float, float, 2);
+        }
+    } else if (dtype == SGPMP_F64) {
         if (M % 4 == 0) UPD(double, double, 4); else UPD(double, double, 2);
     } else if (costs_dtype == SGPMP_F64) {
         if (M % 4 == 0) UPD(float, double, 4); else UPD(float, double, 2);
@@ -103,6 +191,7 @@ hipError_t launch_update(int dtype, int n, int T, int P, int S, const void* cost
         if (M % 4 == 0) UPD(float, float, 4); else UPD(float, float, 2);
     }
 #undef UPD
+#undef UPDQ
     return hipGetLastError();
 }
 

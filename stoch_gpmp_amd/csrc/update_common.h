@@ -293,8 +293,29 @@ static inline size_t regen_lds_bytes(int recipe, int T, int n, int R) {
 // bytes of workgroup scratch (+ regen_lds_bytes behind them when `regen`).  `stats` are ACCUMULATED into by atomics (shard p & 63).
 // VW = elements per thread and load (4 when M % 4 == 0, else 2; M = T * 2n is always even).
 // regen: the particle's rows are NOT in memory (store-free step) -- the rows that carry weight are regenerated (rg says how).
+//
+// NTHR = 64: the update of one particle by ONE WAVE (update_kernel_quad, update.hip: four particles per workgroup, one per wave).
+// `lds_raw` is then the particle's own slice, tid is the lane, and nothing in here waits for another wave: every workgroup
+// barrier is a wave-level fence (upd_sync).  The bits are those of the 256-thread form:
+//  * the element loops (m = tid * VW; m < M; m += nthr * VW -- row gather, partials, finish) sum each element in one thread
+//    in ascending row order, so the thread count does not enter the result;
+//  * the two cross-thread reductions keep the 256-thread association: lane l forms the partial of each virtual thread
+//    l + 64 j (j = 0 .. 3) over s = vt, vt + 256, .., each virtual wave j runs the same xor butterfly 32 .. 1, and the four
+//    results meet in the order j = 0, 1, 2, 3 (red3[] / scratch[] of the 256-thread form);
+//  * no regeneration, no folded end-effector term, and the importance-sampling tail is the CALLER's (one tail for the four
+//    particles of the workgroup, all 256 threads: update_kernel_quad).
 #define SGPMP_UPD_THREADS 256
-template <typename real, typename cost_t, int VW>
+template <int NTHR> __device__ __forceinline__ void upd_sync() {
+    if constexpr (NTHR == 64) {
+        // LDS operations of one wave complete in issue order: what is left to do is keeping the compiler from moving them
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    } else {
+        __syncthreads();
+    }
+}
+template <typename real, typename cost_t, int VW, int NTHR = SGPMP_UPD_THREADS>
 __device__ __forceinline__ void update_particle(int p, int M, int S, const cost_t* c, const real* X, size_t x_pitch,
                                                 real* __restrict__ means, double temperature, double step_size,
                                                 real* __restrict__ weights, real* __restrict__ grad, real* __restrict__ means_prev,
@@ -305,71 +326,127 @@ __device__ __forceinline__ void update_particle(int p, int M, int S, const cost_
                                                 const double* c_add = nullptr) {
     // (rg by reference and a separate flag: a POINTER to the kernel-argument struct made every thread copy the struct to scratch
     // -- 72 bytes of private segment, 16 KB of scratch stores per workgroup: +2.6 us on update_kernel until it was found)
+    static_assert(NTHR == SGPMP_UPD_THREADS || NTHR == 64, "one workgroup or one wave per particle");
+    constexpr bool WAVE = NTHR == 64;
+    constexpr int NVW = SGPMP_UPD_THREADS / 64;                      // (virtual) waves of the 256-thread association
     typedef real vec __attribute__((ext_vector_type(VW)));
     double* w = reinterpret_cast<double*>(lds_raw);                  // [S] weights
     int* idx = reinterpret_cast<int*>(lds_raw + (size_t)S * 8);      // [S] samples with weight != 0
     real* mu_lds = reinterpret_cast<real*>(lds_raw + (((size_t)S * 12 + 15) & ~(size_t)15));   // [M] new means (tail)
     __shared__ double scratch[8];
     __shared__ int nnz_s;
-    const int tid = threadIdx.x < SGPMP_UPD_THREADS ? (int)threadIdx.x : 1 << 30;   // (extra threads: every loop is empty)
-    const int nthr = SGPMP_UPD_THREADS;
+    const int tid = WAVE ? (int)(threadIdx.x & 63) : threadIdx.x < SGPMP_UPD_THREADS ? (int)threadIdx.x : 1 << 30;   // (extra threads: every loop is empty)
+    const int nthr = NTHR;
     // (issued first, consumed last: the four distinct entries of an isotropic prior's one-step precision -- the tail
     // below would otherwise pay two dependent global loads per element)
-    const bool iso_tail = nx.out && nx.isotropic;
+    const bool iso_tail = !WAVE && nx.out && nx.isotropic;
     const int nd = 2 * nx.n;
     const double q00 = iso_tail ? nx.Qinv[0] : 0., q01 = iso_tail ? nx.Qinv[nx.n] : 0.;
     const double q10 = iso_tail ? nx.Qinv[nx.n * nd] : 0., q11 = iso_tail ? nx.Qinv[nx.n * nd + nx.n] : 0.;
 
     // softmax(-c / temperature) exactly as torch.softmax: exp(z - max z) / sum
     double zmax = -1.7976931348623157e308, csum = 0., cmin = 1.7976931348623157e308;
-    for (int s = tid; s < S; s += nthr) {
-        double cv = (double)c[s];
-        if (c_add) cv += c_add[s];                      // (LDS: a cost term the caller evaluated itself -- update_kernel's EeFold)
-        const double z = -cv / temperature;
-        w[s] = z;
-        zmax = z > zmax ? z : zmax;
-        cmin = cv < cmin ? cv : cmin;
-        csum += cv;
-    }
-    // one combined reduction for (max z, sum c, min c): three block reductions cost nine barriers
-    {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = ((blockDim.x < nthr ? blockDim.x : nthr) + 63) >> 6;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const double oz = __shfl_xor(zmax, off, 64), os = __shfl_xor(csum, off, 64), om = __shfl_xor(cmin, off, 64);
-            zmax = oz > zmax ? oz : zmax;
-            csum += os;
-            cmin = om < cmin ? om : cmin;
-        }
-        __shared__ double red3[3 * 4];
-        if (lane == 0 && wave < nw) { red3[wave] = zmax; red3[4 + wave] = csum; red3[8 + wave] = cmin; }
-        __syncthreads();
-        zmax = red3[0]; csum = red3[4]; cmin = red3[8];
-        for (int i = 1; i < nw; ++i) {
-            zmax = red3[i] > zmax ? red3[i] : zmax;
-            csum += red3[4 + i];
-            cmin = red3[8 + i] < cmin ? red3[8 + i] : cmin;
-        }
-    }
-    double part = 0.;
-    for (int s = tid; s < S; s += nthr) {
-        const double e = exp(w[s] - zmax);
-        w[s] = e;
-        part += e;
-    }
     double Z;
-    {   // (one barrier: `scratch` is written once in this kernel)
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = ((blockDim.x < nthr ? blockDim.x : nthr) + 63) >> 6;
+    if constexpr (WAVE) {
+        double zj[NVW], sj[NVW], mj[NVW], c0[NVW];
 #pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off, 64);
-        if (lane == 0 && wave < nw) scratch[wave] = part;
-        __syncthreads();
-        Z = scratch[0];
-        for (int i = 1; i < nw; ++i) Z += scratch[i];
+        for (int j = 0; j < NVW; ++j) c0[j] = tid + 64 * j < S ? (double)c[tid + 64 * j] : 0.;   // (the first trips' loads, all in flight)
+#pragma unroll
+        for (int j = 0; j < NVW; ++j) {
+            double zm = -1.7976931348623157e308, cs = 0., cm = 1.7976931348623157e308;
+            if (64 * j < S) {                             // (a virtual wave without costs reduces to its initial values)
+                for (int s = tid + 64 * j; s < S; s += SGPMP_UPD_THREADS) {
+                    const double cv = s < SGPMP_UPD_THREADS ? c0[j] : (double)c[s];
+                    const double z = -cv / temperature;
+                    w[s] = z;
+                    zm = z > zm ? z : zm;
+                    cm = cv < cm ? cv : cm;
+                    cs += cv;
+                }
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) {
+                    const double oz = __shfl_xor(zm, off, 64), os = __shfl_xor(cs, off, 64), om = __shfl_xor(cm, off, 64);
+                    zm = oz > zm ? oz : zm;
+                    cs += os;
+                    cm = om < cm ? om : cm;
+                }
+            }
+            zj[j] = zm; sj[j] = cs; mj[j] = cm;
+        }
+        zmax = zj[0]; csum = sj[0]; cmin = mj[0];
+#pragma unroll
+        for (int i = 1; i < NVW; ++i) {
+            zmax = zj[i] > zmax ? zj[i] : zmax;
+            csum += sj[i];
+            cmin = mj[i] < cmin ? mj[i] : cmin;
+        }
+        double pj[NVW];
+#pragma unroll
+        for (int j = 0; j < NVW; ++j) {
+            double part = 0.;
+            if (64 * j < S) {
+                for (int s = tid + 64 * j; s < S; s += SGPMP_UPD_THREADS) {   // (each lane reads back what it wrote itself)
+                    const double e = exp(w[s] - zmax);
+                    w[s] = e;
+                    part += e;
+                }
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off, 64);
+            }
+            pj[j] = part;
+        }
+        Z = pj[0];
+#pragma unroll
+        for (int i = 1; i < NVW; ++i) Z += pj[i];
+    } else {
+        for (int s = tid; s < S; s += nthr) {
+            double cv = (double)c[s];
+            if (c_add) cv += c_add[s];                      // (LDS: a cost term the caller evaluated itself -- update_kernel's EeFold)
+            const double z = -cv / temperature;
+            w[s] = z;
+            zmax = z > zmax ? z : zmax;
+            cmin = cv < cmin ? cv : cmin;
+            csum += cv;
+        }
+        // one combined reduction for (max z, sum c, min c): three block reductions cost nine barriers
+        {
+            const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = ((blockDim.x < nthr ? blockDim.x : nthr) + 63) >> 6;
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                const double oz = __shfl_xor(zmax, off, 64), os = __shfl_xor(csum, off, 64), om = __shfl_xor(cmin, off, 64);
+                zmax = oz > zmax ? oz : zmax;
+                csum += os;
+                cmin = om < cmin ? om : cmin;
+            }
+            __shared__ double red3[3 * 4];
+            if (lane == 0 && wave < nw) { red3[wave] = zmax; red3[4 + wave] = csum; red3[8 + wave] = cmin; }
+            __syncthreads();
+            zmax = red3[0]; csum = red3[4]; cmin = red3[8];
+            for (int i = 1; i < nw; ++i) {
+                zmax = red3[i] > zmax ? red3[i] : zmax;
+                csum += red3[4 + i];
+                cmin = red3[8 + i] < cmin ? red3[8 + i] : cmin;
+            }
+        }
+        double part = 0.;
+        for (int s = tid; s < S; s += nthr) {
+            const double e = exp(w[s] - zmax);
+            w[s] = e;
+            part += e;
+        }
+        {   // (one barrier: `scratch` is written once in this kernel)
+            const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = ((blockDim.x < nthr ? blockDim.x : nthr) + 63) >> 6;
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off, 64);
+            if (lane == 0 && wave < nw) scratch[wave] = part;
+            __syncthreads();
+            Z = scratch[0];
+            for (int i = 1; i < nw; ++i) Z += scratch[i];
+        }
     }
     if (stats) {
         const double tot = csum, mn = cmin;
-        if (threadIdx.x == 0) {
+        if (WAVE ? tid == 0 : threadIdx.x == 0) {
             // 64 shards of 4 doubles: a thousand workgroups adding to one address serialise
             // at the memory side (~30 us); the consumer sums the shards
             double* sh = stats + (p & (SGPMP_STAT_SHARDS - 1)) * 4;
@@ -384,25 +461,28 @@ __device__ __forceinline__ void update_particle(int p, int M, int S, const cost_
         w[s] = ws;
         if (weights) weights[(size_t)p * S + s] = (real)ws;
     }
-    __syncthreads();
+    upd_sync<NTHR>();
     // Samples whose weight underflowed to exactly 0 contribute exactly 0 to the sum below, so their
     // rows need not be read at all (with the reference's hyper-parameters the softmax is one-hot
     // and this turns a pass over [S, M] into a pass over one row).  Order-preserving compaction.
-    if (threadIdx.x < 64) {
+    int nnz = 0;
+    if (WAVE || threadIdx.x < 64) {
+        const int ln = (int)(threadIdx.x & 63);
         int base = 0;
         for (int s0 = 0; s0 < S; s0 += 64) {
-            const int s = s0 + (int)threadIdx.x;
+            const int s = s0 + ln;
             const bool nz = s < S && w[s] != 0.;
             const unsigned long long mask = __ballot(nz);
-            const int pos = base + __popcll(mask & ((1ull << threadIdx.x) - 1ull));
+            const int pos = base + __popcll(mask & ((1ull << ln) - 1ull));
             if (nz) idx[pos] = s;
             base += __popcll(mask);
         }
-        if (threadIdx.x == 0) nnz_s = base;
+        if (!WAVE && threadIdx.x == 0) nnz_s = base;
+        nnz = base;                                       // (one wave: every lane has the count)
     }
-    __syncthreads();
-    const int nnz = nnz_s;
-    if (nnz_out && threadIdx.x == 0) *nnz_out = (unsigned)nnz;        // (the next step's fused launch decides on it: FusedArgs::nnz_prev)
+    upd_sync<NTHR>();
+    if constexpr (!WAVE) nnz = nnz_s;
+    if (nnz_out && (WAVE ? tid == 0 : threadIdx.x == 0)) *nnz_out = (unsigned)nnz;   // (the next step's fused launch decides on it: FusedArgs::nnz_prev)
     // Dense-weight regime: the fused launch left softmax partials of the particle's gpp = S / 8 row groups (FusedArgs::part):
     // sum_s w_s (x_s - mu) = sum_j [exp(-cmin_j / temperature - zmax) / Z] acc_j -- gpp rows instead of nnz
     const bool use_part = sizeof(real) == 4 && VW == 4 && partials != nullptr && nnz > gpp;
@@ -410,7 +490,7 @@ __device__ __forceinline__ void update_particle(int p, int M, int S, const cost_
     if (use_part) {
         for (int j = tid; j < gpp; j += nthr)
             coef[j] = exp(-(double)partials[(size_t)j * (M + 4)] / temperature - zmax) * invZ;
-        __syncthreads();
+        upd_sync<NTHR>();
     }
 
     real* mu = means + (size_t)p * M;
@@ -429,7 +509,7 @@ __device__ __forceinline__ void update_particle(int p, int M, int S, const cost_
         if (nx.out) *reinterpret_cast<vec*>(mu_lds + m) = mn;
     };
     bool regenerated = false;
-    if constexpr (sizeof(real) == 4) {
+    if constexpr (sizeof(real) == 4 && !WAVE) {
         if (regen && !use_part) {
             regenerated = true;
             // Store-free step: rounds of R rows with weight -- regenerated into LDS as perturbations y, x = mu + y formed as the
@@ -466,59 +546,90 @@ __device__ __forceinline__ void update_particle(int p, int M, int S, const cost_
             }
         }
     }
-    for (int m = (tid < nthr && !regenerated) ? tid * VW : M; m < M; m += nthr * VW) {
-        const vec mu_m = *reinterpret_cast<const vec*>((mu_rd ? mu_rd : mu) + m);   // (mu_rd: an LDS copy of the same means)
-        double acc[VW];
+    // One wave per particle: a lane has NTHR / 64 times the element groups of a thread of the workgroup form, and taken one after
+    // the other each costs a dependent global round trip (means, row, stores).  The lane keeps U groups in flight instead -- the
+    // loads of all of them first -- with RF rows each; every element is still summed by one lane in ascending row order, one
+    // fma per row, so neither U nor RF enters the bits.  (Groups past M load group m0 again and are dropped.)
+    // The workgroup form has U = 1, RF = 4, PB = 8: one group per trip, never past M, four rows or eight partials in flight
+    // -- the loop update_kernel always had.
+    constexpr int U = WAVE ? 4 : 1, RF = WAVE ? 1 : 4, PB = WAVE ? 1 : 8;
+    for (int m0 = (tid < nthr && !regenerated) ? tid * VW : M; m0 < M; m0 += nthr * VW * U) {
+        int mm[U];
+        vec mu_m[U];
+        double acc[U][VW];
 #pragma unroll
-        for (int i = 0; i < VW; ++i) acc[i] = 0.;
+        for (int g = 0; g < U; ++g) {
+            mm[g] = m0 + g * nthr * VW;
+            if (mm[g] >= M) mm[g] = m0 | (1 << 30);      // (dropped: bit 30 marks it, the loads go to group m0)
+            mu_m[g] = *reinterpret_cast<const vec*>((mu_rd ? mu_rd : mu) + (mm[g] & ~(1 << 30)));   // (mu_rd: an LDS copy of the same means)
+#pragma unroll
+            for (int i = 0; i < VW; ++i) acc[g][i] = 0.;
+        }
         int k = 0;
         if (use_part) {
             if constexpr (sizeof(real) == 4 && VW == 4) {
-                for (int j = 0; j < gpp; j += 8) {           // eight partial rows in flight per thread (S / 8 of them: 16 at config 3)
+                for (int j = 0; j < gpp; j += 8) {           // eight partial rows per trip (S / 8 of them: 16 at config 3), PB x U in flight
                     typedef float f4 __attribute__((ext_vector_type(4)));
-                    f4 v[8];
-                    double cj[8];
+#pragma unroll 2
+                    for (int u0 = 0; u0 < 8; u0 += PB) {
+                        f4 v[PB][U];
+                        double cj[PB];
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int jj = j + u < gpp ? j + u : gpp - 1;
-                        cj[u] = j + u < gpp ? coef[jj] : 0.;
-                        v[u] = *reinterpret_cast<const f4*>(partials + (size_t)jj * (M + 4) + 4 + m);
+                        for (int u = 0; u < PB; ++u) {
+                            const int jj = j + u0 + u < gpp ? j + u0 + u : gpp - 1;
+                            cj[u] = j + u0 + u < gpp ? coef[jj] : 0.;
+#pragma unroll
+                            for (int g = 0; g < U; ++g)
+                                v[u][g] = *reinterpret_cast<const f4*>(partials + (size_t)jj * (M + 4) + 4 + (mm[g] & ~(1 << 30)));
+                        }
+#pragma unroll
+                        for (int u = 0; u < PB; ++u)
+#pragma unroll
+                            for (int g = 0; g < U; ++g)
+#pragma unroll
+                                for (int i = 0; i < VW; ++i) acc[g][i] = fma(cj[u], (double)v[u][g][i], acc[g][i]);
                     }
-#pragma unroll
-                    for (int u = 0; u < 8; ++u)
-#pragma unroll
-                        for (int i = 0; i < VW; ++i) acc[i] = fma(cj[u], (double)v[u][i], acc[i]);
                 }
             }
             k = nnz;                                     // (skip the row gather)
         }
-        for (; k + 4 <= nnz; k += 4) {                   // four rows in flight per thread
-            vec v[4];
-            double ws[4];
+        for (; k + RF <= nnz; k += RF) {                 // RF rows in flight per element group
+            vec v[RF][U];
+            double ws[RF];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
+            for (int u = 0; u < RF; ++u) {
                 const int s = idx[k + u];
                 ws[u] = w[s];
-                v[u] = *reinterpret_cast<const vec*>(X + (size_t)s * x_pitch + m);
+#pragma unroll
+                for (int g = 0; g < U; ++g) v[u][g] = *reinterpret_cast<const vec*>(X + (size_t)s * x_pitch + (mm[g] & ~(1 << 30)));
             }
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
+            for (int u = 0; u < RF; ++u)
 #pragma unroll
-                for (int i = 0; i < VW; ++i) acc[i] = fma(ws[u], (double)(v[u][i] - mu_m[i]), acc[i]);
+                for (int g = 0; g < U; ++g)
+#pragma unroll
+                    for (int i = 0; i < VW; ++i) acc[g][i] = fma(ws[u], (double)(v[u][g][i] - mu_m[g][i]), acc[g][i]);
         }
         for (; k < nnz; ++k) {
             const int s = idx[k];
             const double ws = w[s];
-            const vec v = *reinterpret_cast<const vec*>(X + (size_t)s * x_pitch + m);
+            vec v[U];
 #pragma unroll
-            for (int i = 0; i < VW; ++i) acc[i] = fma(ws, (double)(v[i] - mu_m[i]), acc[i]);
+            for (int g = 0; g < U; ++g) v[g] = *reinterpret_cast<const vec*>(X + (size_t)s * x_pitch + (mm[g] & ~(1 << 30)));
+#pragma unroll
+            for (int g = 0; g < U; ++g)
+#pragma unroll
+                for (int i = 0; i < VW; ++i) acc[g][i] = fma(ws, (double)(v[g][i] - mu_m[g][i]), acc[g][i]);
         }
-        finish(m, mu_m, acc);
+#pragma unroll
+        for (int g = 0; g < U; ++g)
+            if (!(mm[g] >> 30)) finish(mm[g], mu_m[g], acc[g]);
     }
     // The NEXT iteration's importance-sampling weights, from the means just written (K5's arithmetic, same
     // function): sgpmp_step then starts with the sampler + sweep launch instead of a K5 launch, provided the
     // caller vouches that nobody touched the means in between (SGPMP_STEP_MEANS_KEPT).
-    if (nx.out) {
+    // (NTHR = 64: the caller runs ONE tail for the four particles of its workgroup, from the means left in their slices)
+    if (!WAVE && nx.out) {
         __syncthreads();                                  // the new means of this particle are in LDS
         const int d = 2 * nx.n, Tn = M / d;
         const real* mu_new = mu_lds;
