@@ -1583,38 +1583,54 @@ extern "C" int sgpmp_link_distances(sgpmp_ctx* c, const void* frames, int64_t ba
     return SGPMP_OK;
 }
 
+// Value [batch] and gradient [batch, n] of the smooth field term t (spheres, self, voxel or grid distance, end-effector goal) at
+// `batch` configurations: q is [batch, n] (traj_T = 0) or the waypoints 1 .. traj_T - 1 of batch / (traj_T - 1) trajectories
+// [.., traj_T, 2n].  The launches alone: the callers have checked the kind, the FK chain, the spheres and the grid kernels.
+static int term_value_grad(sgpmp_ctx* c, const CostTerm& t, const void* q, long long batch, int traj_T, const void* spheres,
+                           int n_spheres, void* value, void* grad, hipStream_t st) {
+    const int dtype = c->dims.dtype, n = c->dims.n_dof;
+    if (t.kind == SGPMP_COST_GRID_SDF) {                  // a field of the planar point itself: no FK chain
+        HIPCHK(launch_grid_sdf_grad(dtype, n, t, q, batch, traj_T, value, grad, st));
+    } else if (t.kind != SGPMP_COST_EE_GOAL) {
+        HIPCHK(launch_field_grad(dtype, n, t, c->d_chain, c->h_chain.n_joints, q, batch, traj_T, spheres, n_spheres, value,
+                                 grad, st));
+    } else if (traj_T == 0) {
+        HIPCHK(launch_ee_grad(dtype, n, t, c->d_chain, q, batch, 0, 1, 0, value, grad, st));
+    } else {
+        // CostGoal (cost_functions.py:323-337): one row, on the last waypoint -- the other waypoints' entries
+        // of this term's value / gradient arrays are zero rows of the linear system
+        HIPCHK(hipMemsetAsync(value, 0, (size_t)batch * c->esz, st));
+        HIPCHK(hipMemsetAsync(grad, 0, (size_t)batch * n * c->esz, st));
+        HIPCHK(launch_ee_grad(dtype, n, t, c->d_chain, q, batch / (traj_T - 1), traj_T, traj_T - 1, traj_T - 2, value, grad, st));
+    }
+    return SGPMP_OK;
+}
+
 extern "C" int sgpmp_field_grad(sgpmp_ctx* c, int term, const void* q, int64_t batch, const void* spheres,
                                 int n_spheres, void* value, void* grad, void* stream) {
     if (!c || !q || !grad || batch < 0) return fail(SGPMP_EINVAL, "sgpmp_field_grad: bad argument");
     if (!c->have_costs || term < 0 || term >= c->h_prog.n_terms)
         return fail(SGPMP_EINVAL, "sgpmp_field_grad: bad term index");
-    if (c->h_prog.terms[term].kind == SGPMP_COST_GRID_SDF) {     // a field of the planar point itself: no FK chain
+    if (c->h_prog.terms[term].kind == SGPMP_COST_GRID_SDF) {     // (needs neither an FK chain nor the finalized program)
         if (!launch_grid_sdf_grad) return fail(SGPMP_ESTATE, "sgpmp_field_grad: this build has no grid_sdf kernels");
-        HIPCHK(launch_grid_sdf_grad(c->dims.dtype, c->dims.n_dof, c->h_prog.terms[term], q, batch, 0, value, grad,
-                                    (hipStream_t)stream));
-        return SGPMP_OK;
+    } else {
+        if (c->h_prog.terms[term].kind == SGPMP_COST_VOXEL_SDF && !c->have_chain)
+            return fail(SGPMP_ESTATE, "sgpmp_field_grad: the voxel distance term needs an FK chain (sgpmp_set_fk)");
+        if (!c->have_chain) return fail(SGPMP_EINVAL, "sgpmp_field_grad: no FK chain (sgpmp_set_fk)");
+        int rc;
+        if ((rc = finalize_program(c)) != SGPMP_OK) return rc;
+        const CostTerm& t = c->h_prog.terms[term];
+        if (t.kind == SGPMP_COST_SPHERES) {
+            if ((t.flags & 15) == SGPMP_FIELD_OCCUPANCY)
+                return fail(SGPMP_EINVAL, "sgpmp_field_grad: the occupancy count has no gradient (rbf and sdf sphere fields do)");
+            if (!spheres || n_spheres < 1) return fail(SGPMP_EINVAL, "LinkDistanceField cost needs obstacle_spheres");
+        } else if (t.kind != SGPMP_COST_EE_GOAL && t.kind != SGPMP_COST_SELF && t.kind != SGPMP_COST_VOXEL_SDF) {
+            return fail(SGPMP_EINVAL, "sgpmp_field_grad: term is not a smooth link field");
+        }
+        if (t.kind != SGPMP_COST_EE_GOAL && t.n_points > SGPMP_MAX_POINTS)
+            return fail(SGPMP_EINVAL, "too many link points (max 32)");
     }
-    if (c->h_prog.terms[term].kind == SGPMP_COST_VOXEL_SDF && !c->have_chain)
-        return fail(SGPMP_ESTATE, "sgpmp_field_grad: the voxel distance term needs an FK chain (sgpmp_set_fk)");
-    if (!c->have_chain) return fail(SGPMP_EINVAL, "sgpmp_field_grad: no FK chain (sgpmp_set_fk)");
-    int rc;
-    if ((rc = finalize_program(c)) != SGPMP_OK) return rc;
-    CostTerm t = c->h_prog.terms[term];
-    if (t.kind == SGPMP_COST_SPHERES) {
-        if ((t.flags & 15) == SGPMP_FIELD_OCCUPANCY)
-            return fail(SGPMP_EINVAL, "sgpmp_field_grad: the occupancy count has no gradient (rbf and sdf sphere fields do)");
-        if (!spheres || n_spheres < 1) return fail(SGPMP_EINVAL, "LinkDistanceField cost needs obstacle_spheres");
-    } else if (t.kind == SGPMP_COST_EE_GOAL) {
-        HIPCHK(launch_ee_grad(c->dims.dtype, c->dims.n_dof, t, c->d_chain, q, batch, 0, 1, 0, value, grad,
-                              (hipStream_t)stream));
-        return SGPMP_OK;
-    } else if (t.kind != SGPMP_COST_SELF && t.kind != SGPMP_COST_VOXEL_SDF) {
-        return fail(SGPMP_EINVAL, "sgpmp_field_grad: term is not a smooth link field");
-    }
-    if (t.n_points > SGPMP_MAX_POINTS) return fail(SGPMP_EINVAL, "too many link points (max 32)");
-    HIPCHK(launch_field_grad(c->dims.dtype, c->dims.n_dof, t, c->d_chain, c->h_chain.n_joints, q, batch, 0,
-                             spheres, n_spheres, value, grad, (hipStream_t)stream));
-    return SGPMP_OK;
+    return term_value_grad(c, c->h_prog.terms[term], q, batch, 0, spheres, n_spheres, value, grad, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------- GPMP (Gauss-Newton)
@@ -1646,10 +1662,10 @@ static int gpmp_args(sgpmp_ctx* c, GpmpArgs& a, int* field_terms) {
             case SGPMP_COST_SELF:
             case SGPMP_COST_VOXEL_SDF:                    // (a link field like SPHERES: launch_field_grad)
             case SGPMP_COST_GRID_SDF:                     // (a field of the planar point: no FK chain)
-                if (t.kind == SGPMP_COST_GRID_SDF && (t.flags & SGPMP_FLAG_GRID_DISTANCE))
-                    return fail(SGPMP_EINVAL, "GPMP: a grid distance term with SGPMP_FLAG_GRID_DISTANCE is a query, not a cost");
-                if (t.kind == SGPMP_COST_VOXEL_SDF && (t.flags & SGPMP_FLAG_GRID_DISTANCE))
-                    return fail(SGPMP_EINVAL, "GPMP: a voxel distance term with SGPMP_FLAG_GRID_DISTANCE is a query, not a cost");
+                if ((t.kind == SGPMP_COST_GRID_SDF || t.kind == SGPMP_COST_VOXEL_SDF) && (t.flags & SGPMP_FLAG_GRID_DISTANCE))
+                    return fail(SGPMP_EINVAL, t.kind == SGPMP_COST_GRID_SDF
+                        ? "GPMP: a grid distance term with SGPMP_FLAG_GRID_DISTANCE is a query, not a cost"
+                        : "GPMP: a voxel distance term with SGPMP_FLAG_GRID_DISTANCE is a query, not a cost");
                 if (a.n_fields == 4) return fail(SGPMP_EINVAL, "GPMP: more than 4 link-field terms");
                 field_terms[a.n_fields] = i;
                 a.f[a.n_fields].K = t.K;
@@ -1732,59 +1748,31 @@ extern "C" int sgpmp_gpmp_linearize(sgpmp_ctx* c, const void* means, const void*
     }
     if ((rc = gpmp_alloc(c, a)) != SGPMP_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (c->gdense.on) {
-        // the same two launches per term on the FINE states 1 .. T_f - 1 of the interpolated means; the rows the solve builds
-        // from them and the limit rows enter diag_sum through gpmp_dense_diag_kernel
-        GpmpDenseArgs& da = c->gdense.k;
-        const int Tf = da.Tf;
-        const long long Bf = (long long)a.P * (Tf - 1);
-        for (int k = 0; k < a.n_fields; ++k) {
-            const CostTerm& t = c->h_prog.terms[ft[k]];
-            if (t.kind == SGPMP_COST_SPHERES && (!spheres || n_spheres < 1))
-                return fail(SGPMP_EINVAL, "LinkDistanceField cost needs obstacle_spheres");
-        }
-        if (a.n_fields > 0 && a.P > 0)
-            HIPCHK(launch_gpmp_fine(c->dims.dtype, a.n, a.T, means, a.P, da.n_sub, da.dt, c->d_gfine, st));
-        for (int k = 0; k < a.n_fields; ++k) {
-            const CostTerm& t = c->h_prog.terms[ft[k]];
-            da.inserted[k] = t.kind == SGPMP_COST_EE_GOAL ? 0 : 1;
-            if (t.kind == SGPMP_COST_EE_GOAL) {
-                HIPCHK(hipMemsetAsync(c->d_fval[k], 0, (size_t)Bf * c->esz, st));
-                HIPCHK(hipMemsetAsync(c->d_fgrad[k], 0, (size_t)Bf * a.n * c->esz, st));
-                HIPCHK(launch_ee_grad(c->dims.dtype, a.n, t, c->d_chain, c->d_gfine, a.P, Tf, Tf - 1, Tf - 2, c->d_fval[k],
-                                      c->d_fgrad[k], st));
-            } else if (t.kind == SGPMP_COST_GRID_SDF)
-                HIPCHK(launch_grid_sdf_grad(c->dims.dtype, a.n, t, c->d_gfine, Bf, Tf, c->d_fval[k], c->d_fgrad[k], st));
-            else
-                HIPCHK(launch_field_grad(c->dims.dtype, a.n, t, c->d_chain, c->h_chain.n_joints, c->d_gfine, Bf, Tf, spheres,
-                                         n_spheres, c->d_fval[k], c->d_fgrad[k], st));
-            a.f[k].val = c->d_fval[k];
-            a.f[k].grad = c->d_fgrad[k];
-        }
-        if (diag_sum) HIPCHK(launch_gpmp_dense_diag(c->dims.dtype, a, da, means, diag_sum, st));
-        return SGPMP_OK;
-    }
-    const long long B = (long long)a.P * (a.T - 1);
+    for (int k = 0; k < a.n_fields; ++k)
+        if (c->h_prog.terms[ft[k]].kind == SGPMP_COST_SPHERES && (!spheres || n_spheres < 1))
+            return fail(SGPMP_EINVAL, "LinkDistanceField cost needs obstacle_spheres");
+    // every term's value and gradient on the states 1 .. traj_T - 1 of q: the waypoints of the means, or with continuous-time
+    // factors the FINE states of the interpolated means (the rows the solve builds from them and the limit rows enter diag_sum
+    // through gpmp_dense_diag_kernel)
+    GpmpDenseArgs& da = c->gdense.k;
+    const bool dense = c->gdense.on;
+    const void* q = dense ? c->d_gfine : means;
+    const int traj_T = dense ? da.Tf : a.T;
+    if (dense && a.n_fields > 0 && a.P > 0)
+        HIPCHK(launch_gpmp_fine(c->dims.dtype, a.n, a.T, means, a.P, da.n_sub, da.dt, c->d_gfine, st));
     for (int k = 0; k < a.n_fields; ++k) {
         const CostTerm& t = c->h_prog.terms[ft[k]];
-        if (t.kind == SGPMP_COST_SPHERES && (!spheres || n_spheres < 1))
-            return fail(SGPMP_EINVAL, "LinkDistanceField cost needs obstacle_spheres");
-        if (t.kind == SGPMP_COST_EE_GOAL) {
-            // CostGoal (cost_functions.py:323-337): one row, on the last waypoint -- the other waypoints' entries
-            // of this term's value / gradient arrays are zero rows of the linear system
-            HIPCHK(hipMemsetAsync(c->d_fval[k], 0, (size_t)B * c->esz, st));
-            HIPCHK(hipMemsetAsync(c->d_fgrad[k], 0, (size_t)B * a.n * c->esz, st));
-            HIPCHK(launch_ee_grad(c->dims.dtype, a.n, t, c->d_chain, means, a.P, a.T, a.T - 1, a.T - 2, c->d_fval[k],
-                                  c->d_fgrad[k], st));
-        } else if (t.kind == SGPMP_COST_GRID_SDF)
-            HIPCHK(launch_grid_sdf_grad(c->dims.dtype, a.n, t, means, B, a.T, c->d_fval[k], c->d_fgrad[k], st));
-        else
-        HIPCHK(launch_field_grad(c->dims.dtype, a.n, t, c->d_chain, c->h_chain.n_joints, means, B, a.T, spheres,
-                                 n_spheres, c->d_fval[k], c->d_fgrad[k], st));
+        if (dense) da.inserted[k] = t.kind == SGPMP_COST_EE_GOAL ? 0 : 1;
+        if ((rc = term_value_grad(c, t, q, (long long)a.P * (traj_T - 1), traj_T, spheres, n_spheres, c->d_fval[k],
+                                  c->d_fgrad[k], st)) != SGPMP_OK)
+            return rc;
         a.f[k].val = c->d_fval[k];
         a.f[k].grad = c->d_fgrad[k];
     }
-    if (diag_sum) HIPCHK(launch_gpmp_diag(c->dims.dtype, a, diag_sum, st));
+    if (diag_sum) {
+        if (dense) HIPCHK(launch_gpmp_dense_diag(c->dims.dtype, a, da, means, diag_sum, st));
+        else HIPCHK(launch_gpmp_diag(c->dims.dtype, a, diag_sum, st));
+    }
     return SGPMP_OK;
 }
 

@@ -406,7 +406,7 @@ hipError_t launch_gpmp_dense_diag(int dtype, const GpmpArgs& a, const GpmpDenseA
                                   hipStream_t stream) __attribute__((weak));
 hipError_t launch_gpmp_dense_solve(int dtype, const GpmpArgs& a, const GpmpDenseArgs& da, void* means, void* d_theta,
                                    void* costs, hipStream_t stream) __attribute__((weak));
-// SGPMP_COST_GRID_SDF (grid_sdf.hip): hinge value [batch] and gradient [batch, n] (entries >= 2 zero) of the term at the planar
+// SGPMP_COST_GRID_SDF (sdf.hip): hinge value [batch] and gradient [batch, n] (entries >= 2 zero) of the term at the planar
 // point (q[0], q[1]); q laid out as launch_field_grad's (traj_T = 0: [B, n]; traj_T = T: waypoints 1 .. T-1 of [P, T, 2n]).
 // Weak for the same reason: sgpmp_field_grad and the GPMP linearisation refuse the kind where the definition is absent.
 hipError_t launch_grid_sdf_grad(int dtype, int n, const CostTerm& term, const void* q, long long batch, int traj_T, void* value,

@@ -551,43 +551,35 @@ class Engine:
                                               L.ptr(value), L.ptr(grad), L.stream_ptr()))
         return value, grad
 
+    def _sdf_build(self, entry_point, ndim, occ, cell, threshold, out):
+        """`entry_point` (sgpmp_grid_sdf_build, ndim 2, or sgpmp_voxel_sdf_build, ndim 3) on occ, into `out` or a new tensor."""
+        name, axes = entry_point[len("sgpmp_"):], "[ny, nx]" if ndim == 2 else "[nz, ny, nx]"
+        self._chk(occ, "occ")
+        if occ.dim() != ndim:
+            raise ValueError(f"{name}: occ must be {axes}")
+        shape = tuple(int(v) for v in occ.shape)
+        if out is None:
+            out = torch.empty(*shape, **self.tensor_args)
+        else:
+            self._chk(out, "out")
+            if tuple(out.shape) != shape:
+                raise ValueError(f"{name}: out must have occ's shape")
+        with torch.cuda.device(self.device):
+            L.check(getattr(self.lib, entry_point)(self._ctx, L.ptr(occ) if occ.numel() else None, *shape, float(cell),
+                                                   float(threshold), L.ptr(out) if out.numel() else None, L.stream_ptr()))
+        return out
+
     def grid_sdf_build(self, occ, cell, threshold=0., out=None):
         """Signed distance grid [ny, nx] of the occupancy grid occ [ny, nx] (device tensors of this engine's dtype): the exact
         Euclidean distance transform in two launches on the current stream (include/sgpmp.h: sgpmp_grid_sdf_build; host-side
         twin: stoch_gpmp_amd/grid_sdf.py).  `out`: a tensor to rebuild in place."""
-        self._chk(occ, "occ")
-        if occ.dim() != 2:
-            raise ValueError("grid_sdf_build: occ must be [ny, nx]")
-        ny, nx = int(occ.shape[0]), int(occ.shape[1])
-        if out is None:
-            out = torch.empty(ny, nx, **self.tensor_args)
-        else:
-            self._chk(out, "out")
-            if tuple(out.shape) != (ny, nx):
-                raise ValueError("grid_sdf_build: out must have occ's shape")
-        with torch.cuda.device(self.device):
-            L.check(self.lib.sgpmp_grid_sdf_build(self._ctx, L.ptr(occ) if occ.numel() else None, ny, nx, float(cell),
-                                                  float(threshold), L.ptr(out) if out.numel() else None, L.stream_ptr()))
-        return out
+        return self._sdf_build("sgpmp_grid_sdf_build", 2, occ, cell, threshold, out)
 
     def voxel_sdf_build(self, occ, cell, threshold=0., out=None):
         """Signed distance volume [nz, ny, nx] of the occupancy volume occ [nz, ny, nx] (device tensors of this engine's dtype):
         the exact Euclidean distance transform in three launches on the current stream, in place in the output (include/sgpmp.h:
         sgpmp_voxel_sdf_build; host-side twin: stoch_gpmp_amd/voxel_sdf.py).  `out`: a tensor to rebuild in place."""
-        self._chk(occ, "occ")
-        if occ.dim() != 3:
-            raise ValueError("voxel_sdf_build: occ must be [nz, ny, nx]")
-        nz, ny, nx = (int(v) for v in occ.shape)
-        if out is None:
-            out = torch.empty(nz, ny, nx, **self.tensor_args)
-        else:
-            self._chk(out, "out")
-            if tuple(out.shape) != (nz, ny, nx):
-                raise ValueError("voxel_sdf_build: out must have occ's shape")
-        with torch.cuda.device(self.device):
-            L.check(self.lib.sgpmp_voxel_sdf_build(self._ctx, L.ptr(occ) if occ.numel() else None, nz, ny, nx, float(cell),
-                                                   float(threshold), L.ptr(out) if out.numel() else None, L.stream_ptr()))
-        return out
+        return self._sdf_build("sgpmp_voxel_sdf_build", 3, occ, cell, threshold, out)
 
     # ------------------------------------------------------------------ dense trajectories
     def interpolate(self, trajs, n_sub, dt):

@@ -13,6 +13,7 @@ import torch
 
 from .. import _lib as L
 from ..engine import Engine
+from .sdf_field import DeviceSdf
 
 
 class ObstacleRectangle:
@@ -138,11 +139,11 @@ class ObstacleMap:
         return GridDistanceField(self, margin, threshold=threshold)
 
 
-class GridDistanceField:
+class GridDistanceField(DeviceSdf):
     """Signed-distance grid of an ObstacleMap under the GPMP hinge, h = max(margin - d, 0) with d the bilinear interpolation of
     the map's exact Euclidean signed distance (include/sgpmp.h: SGPMP_COST_GRID_SDF) -- the smooth field of a planar map scene:
     CostCollision(field=...) accepts it in StochGPMP and, unlike the occupancy lookup, in GPMP, `continuous_cost` and
-    `get_linear_system`.  No reference counterpart.  The grid is built on the device (csrc/grid_sdf.hip); after editing the map
+    `get_linear_system`.  No reference counterpart.  The grid is built on the device (csrc/sdf.hip); after editing the map
     (`obst_map.map`, then `convert_map()`), `update()` rebuilds it."""
     works_on_frames = False          # compute_cost takes points [..., 2]
     needs_fk_chain = False           # FieldFactor: the Jacobian is with respect to the point itself
@@ -156,8 +157,6 @@ class GridDistanceField:
         self.tensor_args = obst_map.tensor_args
         self._version = 0            # edit counter: planners re-compile their cost program when it moves
         self._engines = {}
-        self._build_engine = None
-        self.sdf = None
         self._build()
 
     def _build(self):
@@ -166,25 +165,12 @@ class GridDistanceField:
             om.convert_map()
         L.require_cuda(self.tensor_args)
         occ = om.map_torch
-        key = (occ.dtype, str(occ.device))
-        if self._build_engine is None or self._build_engine[0] != key:        # one context for every rebuild
-            self._build_engine = (key, Engine(2, 2, 0, 1, tensor_args={"device": occ.device, "dtype": occ.dtype}))
-        in_place = self.sdf is not None and self.sdf.shape == occ.shape and self.sdf.dtype == occ.dtype and \
-            self.sdf.device == occ.device
-        self.sdf = self._build_engine[1].grid_sdf_build(occ, om.cell_size, self.threshold, out=self.sdf if in_place else None)
-        if in_place:
+        if self._rebuild("grid_sdf_build", 2, occ, om.cell_size):
             # the query engines of the grid's own dtype point at this very tensor: still valid.  Those of another dtype hold a
             # converted copy (Engine.set_costs), which is stale now
             self._engines = {k: e for k, e in self._engines.items() if (k[1] if k[0] == "grad" else k[0]) == occ.dtype}
         else:
             self._engines = {}
-
-    def update(self):
-        """Rebuild the distance grid from the map's current `map_torch` (two launches, stream-ordered) and tell every planner
-        holding this field to re-compile its cost program before its next step."""
-        self._build()
-        self._version += 1
-        return self.sdf
 
     def descriptor(self, sigma):
         om = self.obst_map

@@ -3,7 +3,7 @@ boxes, anything that arrives as an occupancy volume).  No reference counterpart.
 
 `VoxelMap` holds the occupancy volume [nz, ny, nx] on the device; `VoxelDistanceField` is the hinge on its exact Euclidean
 signed distance at the link points of an FK chain (include/sgpmp.h: SGPMP_COST_VOXEL_SDF), built on the device by
-csrc/voxel_sdf.hip and evaluated by `voxel_sdf_field` (csrc/cost_device.h).  Host-side twin: stoch_gpmp_amd/voxel_sdf.py.
+csrc/sdf.hip and evaluated by `voxel_sdf_field` (csrc/cost_device.h).  Host-side twin: stoch_gpmp_amd/voxel_sdf.py.
 """
 from math import ceil
 
@@ -13,6 +13,7 @@ import torch
 from .. import _lib as L
 from ..costs.fields import DistanceField, _linspace_alpha
 from ..engine import Engine
+from .sdf_field import DeviceSdf
 
 
 class VoxelMap:
@@ -78,7 +79,7 @@ class VoxelMap:
         return VoxelDistanceField(self, margin, threshold=threshold, **kwargs)
 
 
-class VoxelDistanceField(DistanceField):
+class VoxelDistanceField(DeviceSdf, DistanceField):
     """Hinge on a voxel signed-distance field, summed over the link points of the FK chain: f(q) = sum_p max(margin - d(p), 0),
     d the trilinear interpolation of the volume's exact Euclidean signed distance -- the GPMP obstacle field for scenes given as
     occupancy.  The point set is LinkDistanceField's (every link origin + `num_interpolate` points per link pair of
@@ -97,27 +98,11 @@ class VoxelDistanceField(DistanceField):
         self.threshold = float(threshold)
         self.num_interpolate = num_interpolate
         self.link_interpolate_range = link_interpolate_range
-        self._build_engine = None
-        self.sdf = None
         self._build()
 
     def _build(self):
-        occ = self.voxel_map.occ.contiguous()
-        key = (occ.dtype, str(occ.device))
-        if self._build_engine is None or self._build_engine[0] != key:        # one context for every rebuild
-            self._build_engine = (key, Engine(1, 2, 0, 1, tensor_args={"device": occ.device, "dtype": occ.dtype}))
-        in_place = self.sdf is not None and self.sdf.shape == occ.shape and self.sdf.dtype == occ.dtype and \
-            self.sdf.device == occ.device
-        self.sdf = self._build_engine[1].voxel_sdf_build(occ, self.voxel_map.cell_size, self.threshold,
-                                                         out=self.sdf if in_place else None)
+        self._rebuild("voxel_sdf_build", 1, self.voxel_map.occ.contiguous(), self.voxel_map.cell_size)
         self._engines = {}           # the query engines hold the old tensor (or a converted copy of it)
-
-    def update(self):
-        """Rebuild the distance volume from the map's current `occ` (three launches, stream-ordered) and tell every planner
-        holding this field to re-compile its cost program before its next step."""
-        self._build()
-        self._version += 1
-        return self.sdf
 
     def descriptor(self, sigma, distance=False):
         vm = self.voxel_map

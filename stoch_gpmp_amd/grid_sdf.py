@@ -1,56 +1,23 @@
 """Host-side twin (numpy) of the signed-distance grid field, SGPMP_COST_GRID_SDF (include/sgpmp.h has the definition;
-csrc/grid_sdf.hip builds the grid on the device, `grid_sdf_field` in csrc/cost_device.h evaluates it) -- what dense.py is for
+csrc/sdf.hip builds the grid on the device, `grid_sdf_field` in csrc/cost_device.h evaluates it) -- what dense.py is for
 the dense trajectories: the same arithmetic in the same order, for tests, examples and host-side checks.  No reference
 counterpart: the reference's ObstacleMap is occupancy only.
 """
 import numpy as np
 
-_NONE = 8192                         # csrc/grid_sdf.hip SDF_NONE: "this column has no such cell"
+from .sdf import clamp, signed_distance
+
 MAX_DIM = 4096
-
-
-def _column_distance(mask):
-    """mask [ny, nx] bool -> per cell the distance in cells, along its column, to the nearest True cell (_NONE: none)."""
-    ny, nx = mask.shape
-    out = np.full((ny, nx), _NONE, dtype=np.int64)
-    run = np.full(nx, _NONE, dtype=np.int64)
-    for y in range(ny):
-        run = np.where(mask[y], 0, np.minimum(run + 1, _NONE))
-        out[y] = run
-    run = np.full(nx, _NONE, dtype=np.int64)
-    for y in range(ny - 1, -1, -1):
-        run = np.where(mask[y], 0, np.minimum(run + 1, _NONE))
-        out[y] = np.minimum(out[y], run)
-    return out
-
-
-def _squared_distance(mask):
-    """Exact squared Euclidean distance (in cells, an integer) from every cell to the nearest True cell; >= _NONE^2: none."""
-    g = _column_distance(mask)
-    ny, nx = mask.shape
-    xs = np.arange(nx, dtype=np.int64)
-    dx2 = (xs[:, None] - xs[None, :]) ** 2                    # [x, x']
-    out = np.empty((ny, nx), dtype=np.int64)
-    for y in range(ny):
-        out[y] = (dx2 + (g[y] ** 2)[None, :]).min(axis=1)
-    return out
+_BAD_OCC = "signed_distance_grid: occ must be [ny, nx] with 1 <= ny, nx <= 4096 and cell > 0"
 
 
 def signed_distance_grid(occ, cell, threshold=0.):
     """occ [ny, nx] -> sdf [ny, nx] (float64): the signed Euclidean distance at cell centres in world units, (D - 0.5) * cell
     for a free cell (D: distance between index pairs to the nearest occupied cell) and -(D - 0.5) * cell for an occupied one
     (D to the nearest free cell); +/- cell * (nx + ny) where there is no such cell.  A cell is occupied when occ > threshold."""
-    occ = np.asarray(occ)
-    if occ.ndim != 2 or not (1 <= occ.shape[0] <= MAX_DIM and 1 <= occ.shape[1] <= MAX_DIM) or not cell > 0:
-        raise ValueError("signed_distance_grid: occ must be [ny, nx] with 1 <= ny, nx <= 4096 and cell > 0")
-    o = occ.astype(np.float64) > float(threshold)
-    ny, nx = o.shape
-    cap = float(cell) * float(nx + ny)
-    to_occ, to_free = _squared_distance(o), _squared_distance(~o)
-    d2 = np.where(o, to_free, to_occ)
-    s = (np.sqrt(d2.astype(np.float64)) - 0.5) * float(cell)
-    s = np.where(d2 >= _NONE * _NONE, cap, s)
-    return np.where(o, -s, s)
+    if np.ndim(occ) != 2:
+        raise ValueError(_BAD_OCC)
+    return signed_distance(occ, cell, threshold, MAX_DIM, _BAD_OCC)
 
 
 def field(sdf, xy, cell, offset, margin):
@@ -67,10 +34,6 @@ def field(sdf, xy, cell, offset, margin):
         v = (xy[..., 1] * inv + real(offset[1])) - real(0.5)
         fu, fv = np.floor(u), np.floor(v)
         fx, fy = u - fu, v - fv
-
-        def clamp(a, hi):
-            a = np.where(np.isnan(a), 0., a)
-            return np.minimum(np.maximum(a, 0.), hi).astype(np.int64)
         i0, i1 = clamp(fu, nx - 1), clamp(fu + real(1.), nx - 1)
         j0, j1 = clamp(fv, ny - 1), clamp(fv + real(1.), ny - 1)
         s00, s10, s01, s11 = sdf[j0, i0], sdf[j0, i1], sdf[j1, i0], sdf[j1, i1]

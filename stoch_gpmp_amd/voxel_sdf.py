@@ -1,31 +1,14 @@
 """Host-side twin (numpy) of the voxel signed-distance field, SGPMP_COST_VOXEL_SDF (include/sgpmp.h has the definition;
-csrc/voxel_sdf.hip builds the volume on the device, `voxel_sdf_field` in csrc/cost_device.h evaluates it) -- what grid_sdf.py is
+csrc/sdf.hip builds the volume on the device, `voxel_sdf_field` in csrc/cost_device.h evaluates it) -- what grid_sdf.py is
 for the planar field: the same arithmetic in the same order, for tests, examples and host-side checks.  No reference counterpart.
 """
 import numpy as np
 
-_NONE = 1 << 20                      # csrc/voxel_sdf.hip VOX_NONE: "there is no such cell" (> 3 * 511^2, exact in fp32)
+from .sdf import clamp, signed_distance
+
 MAX_DIM = 512
-
-
-def _axis_pass(g, axis):
-    """g: squared distances (int64, _NONE: none) -> min over a' along `axis` of (a - a')^2 + g[a'], capped at _NONE."""
-    g = np.moveaxis(g, axis, -1)
-    n = g.shape[-1]
-    idx = np.arange(n, dtype=np.int64)
-    d2 = (idx[:, None] - idx[None, :]) ** 2                   # [a, a']
-    out = np.empty_like(g)
-    for a in range(n):                                        # (a loop over the axis keeps the temporary at the volume's size)
-        out[..., a] = (g + d2[a]).min(axis=-1)
-    return np.moveaxis(np.minimum(out, _NONE), -1, axis)
-
-
-def _squared_distance(mask):
-    """Exact squared Euclidean distance (in cells, an integer) from every cell to the nearest True cell; _NONE: none."""
-    g = np.where(mask, 0, _NONE).astype(np.int64)
-    for axis in (0, 1, 2):                                    # z, y, x: the device's three passes
-        g = _axis_pass(g, axis)
-    return g
+_BAD_OCC = ("signed_distance_volume: occ must be [nz, ny, nx] with 1 <= nz, ny, nx <= 512, cell > 0 and a threshold "
+            "that is not NaN")
 
 
 def signed_distance_volume(occ, cell, threshold=0.):
@@ -33,16 +16,9 @@ def signed_distance_volume(occ, cell, threshold=0.):
     (sqrt(D2) - 0.5) * cell for a free cell (D2: squared distance between index triples to the nearest occupied cell) and
     -(sqrt(D2) - 0.5) * cell for an occupied one (D2 to the nearest free cell); +/- cell * (nx + ny + nz) where there is no such
     cell.  A cell is occupied when occ > threshold."""
-    occ = np.asarray(occ)
-    if occ.ndim != 3 or not all(1 <= n <= MAX_DIM for n in occ.shape) or not cell > 0 or threshold != threshold:
-        raise ValueError("signed_distance_volume: occ must be [nz, ny, nx] with 1 <= nz, ny, nx <= 512, cell > 0 and a threshold "
-                         "that is not NaN")
-    o = occ.astype(np.float64) > float(threshold)
-    cap = float(cell) * float(sum(o.shape))
-    d2 = np.where(o, _squared_distance(~o), _squared_distance(o))
-    s = (np.sqrt(d2.astype(np.float64)) - 0.5) * float(cell)
-    s = np.where(d2 >= _NONE, cap, s)
-    return np.where(o, -s, s)
+    if np.ndim(occ) != 3 or threshold != threshold:
+        raise ValueError(_BAD_OCC)
+    return signed_distance(occ, cell, threshold, MAX_DIM, _BAD_OCC)
 
 
 def _interp(sdf, cell, origin, pts):
@@ -58,10 +34,6 @@ def _interp(sdf, cell, origin, pts):
     w = (pts[..., 2] * inv + real(origin[2])) - real(0.5)
     fu, fv, fw = np.floor(u), np.floor(v), np.floor(w)
     fx, fy, fz = u - fu, v - fv, w - fw
-
-    def clamp(a, hi):
-        a = np.where(np.isnan(a), 0., a)
-        return np.minimum(np.maximum(a, 0.), hi).astype(np.int64)
     i0, i1 = clamp(fu, nx - 1), clamp(fu + real(1.), nx - 1)
     j0, j1 = clamp(fv, ny - 1), clamp(fv + real(1.), ny - 1)
     k0, k1 = clamp(fw, nz - 1), clamp(fw + real(1.), nz - 1)

@@ -1,49 +1,10 @@
 """Test-side oracle of the signed-distance grid field (SGPMP_COST_GRID_SDF), straight from the definition in include/sgpmp.h:
-a brute-force O(N^2) numpy distance transform, and the bilinear hinge in torch fp64 whose gradient comes from autograd.
-Shares no code with stoch_gpmp_amd/grid_sdf.py or the kernels."""
+the distance transform of tests/sdf_oracle.py (brute force, scipy), and the bilinear hinge in torch fp64 whose gradient comes from
+autograd.  Shares no code with stoch_gpmp_amd/grid_sdf.py or the kernels."""
 import numpy as np
 import torch
 
-
-def brute_sdf(occ, cell, threshold=0.):
-    """Every cell against every cell of the other kind: integer squared index distances, one sqrt in double, (D - 0.5) * cell."""
-    o = np.asarray(occ, dtype=np.float64) > threshold
-    ny, nx = o.shape
-    cap = cell * (nx + ny)
-    jj, ii = np.meshgrid(np.arange(ny), np.arange(nx), indexing="ij")
-    pts = np.stack((jj.ravel(), ii.ravel()), 1).astype(np.int64)
-    flat = o.ravel()
-    out = np.empty(ny * nx)
-    for kind in (False, True):                                 # cells of this kind look for the nearest cell of the other
-        mine, other = pts[flat == kind], pts[flat != kind]
-        if len(mine) == 0:
-            continue
-        if len(other) == 0:
-            out[flat == kind] = -cap if kind else cap
-            continue
-        best = np.empty(len(mine), dtype=np.int64)
-        for a in range(0, len(mine), 512):
-            d = mine[a:a + 512, None, :] - other[None, :, :]
-            best[a:a + 512] = (d * d).sum(-1).min(1)
-        s = (np.sqrt(best.astype(np.float64)) - 0.5) * cell
-        out[flat == kind] = -s if kind else s
-    return out.reshape(ny, nx)
-
-
-def scipy_sdf(occ, cell, threshold=0.):
-    """The same grid from scipy's exact Euclidean transform (for maps where the brute force is slow)."""
-    from scipy.ndimage import distance_transform_edt
-    o = np.asarray(occ, dtype=np.float64) > threshold
-    ny, nx = o.shape
-    cap = cell * (nx + ny)
-    if not o.any():
-        return np.full(o.shape, cap)
-    if o.all():
-        return np.full(o.shape, -cap)
-    # (squared integer distances back from the transform's doubles: exact below 2^53, so the one sqrt is the definition's)
-    d_out = np.rint(distance_transform_edt(~o) ** 2)
-    d_in = np.rint(distance_transform_edt(o) ** 2)
-    return np.where(o, -(np.sqrt(d_in) - 0.5) * cell, (np.sqrt(d_out) - 0.5) * cell)
+from tests.sdf_oracle import brute_sdf, scipy_sdf  # noqa: F401  (the transform: the tests reach it through this module)
 
 
 def field_torch(sdf, xy, cell, offset, margin):
@@ -119,6 +80,10 @@ def small_maps():
     two = np.array([[0., 1.], [1., 0.]])
     row = np.zeros((1, 7)); row[0, 2] = 1.; row[0, 3] = 1.
     col = np.zeros((7, 1)); col[5, 0] = 1.
+    # the one transform behind grid and volume: runs past a volume's 512-cell capacity along either axis, and columns whose
+    # scan meets the sentinel on one side
+    long_row = np.zeros((1, 600)); long_row[0, 0] = 1.
+    stripes = np.zeros((2, 600)); stripes[0] = 1.
     return {
         "1x1 free": (np.zeros((1, 1)), 0.5),
         "1x1 occupied": (np.ones((1, 1)), 0.5),
@@ -128,6 +93,9 @@ def small_maps():
         "20x24 box and disc": (box_disc_map()[0], box_disc_map()[1]),
         "corner cell": (corner, 0.3),
         "70x130 random": ((rng.uniform(size=(70, 130)) < 0.3).astype(np.float64), 0.05),
+        "1x600": (long_row, 0.1),
+        "600x1": (long_row.T.copy(), 0.1),
+        "2x600": (stripes, 0.1),
     }
 
 

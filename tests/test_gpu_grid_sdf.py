@@ -1,4 +1,4 @@
-"""The signed-distance grid field (SGPMP_COST_GRID_SDF) on the GPU: the distance transform (csrc/grid_sdf.hip), the term in
+"""The signed-distance grid field (SGPMP_COST_GRID_SDF) on the GPU: the distance transform (csrc/sdf.hip), the term in
 sgpmp_field_grad, the sweep, the step, sgpmp_dense_cost / sgpmp_dense_cost_grad and GPMP with and without continuous-time factors,
 against the test-side oracle (tests/grid_sdf_oracle.py: brute force / scipy transform, torch fp64 field with autograd) and the
 numpy twin (stoch_gpmp_amd/grid_sdf.py).  Needs the MI355X: run with `-m gpu`.

@@ -1,4 +1,4 @@
-"""The voxel signed-distance field (SGPMP_COST_VOXEL_SDF) on the GPU: the distance transform (csrc/voxel_sdf.hip), the term in
+"""The voxel signed-distance field (SGPMP_COST_VOXEL_SDF) on the GPU: the distance transform (csrc/sdf.hip), the term in
 sgpmp_field_grad, sgpmp_field_eval, the generic sweep on its three FK flavours, the step, and GPMP with and without
 continuous-time factors, against the test-side oracle (tests/voxel_sdf_oracle.py: brute force / scipy transform, torch fp64 field
 with autograd through oracle/fk.py).  Needs the MI355X: run with `-m gpu`.

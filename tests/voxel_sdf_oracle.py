@@ -1,52 +1,12 @@
 """Test-side oracle of the voxel signed-distance field (SGPMP_COST_VOXEL_SDF), straight from the definition in include/sgpmp.h:
-a brute-force numpy distance transform, scipy's exact transform, and the trilinear hinge over the link points in torch fp64 whose
+the distance transform of tests/sdf_oracle.py (brute force, scipy), and the trilinear hinge over the link points in torch fp64 whose
 gradient comes from autograd through oracle/fk.py.  Shares no code with stoch_gpmp_amd/voxel_sdf.py or the kernels."""
 import numpy as np
 import torch
 
 from oracle import ref_equiv as R
 from oracle.fk import PANDA_CHAIN, fk_all_links
-
-
-# ------------------------------------------------------------------------------------------------ the transform
-def brute_sdf(occ, cell, threshold=0.):
-    """Every cell against every cell of the other kind: integer squared index distances, one sqrt in double, (D - 0.5) * cell."""
-    o = np.asarray(occ, dtype=np.float64) > threshold
-    nz, ny, nx = o.shape
-    cap = cell * (nx + ny + nz)
-    kk, jj, ii = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
-    pts = np.stack((kk.ravel(), jj.ravel(), ii.ravel()), 1).astype(np.int64)
-    flat = o.ravel()
-    out = np.empty(flat.size)
-    for kind in (False, True):                                 # cells of this kind look for the nearest cell of the other
-        mine, other = pts[flat == kind], pts[flat != kind]
-        if len(mine) == 0:
-            continue
-        if len(other) == 0:
-            out[flat == kind] = -cap if kind else cap
-            continue
-        best = np.empty(len(mine), dtype=np.int64)
-        for a in range(0, len(mine), 256):
-            d = mine[a:a + 256, None, :] - other[None, :, :]
-            best[a:a + 256] = (d * d).sum(-1).min(1)
-        s = (np.sqrt(best.astype(np.float64)) - 0.5) * cell
-        out[flat == kind] = -s if kind else s
-    return out.reshape(nz, ny, nx)
-
-
-def scipy_sdf(occ, cell, threshold=0.):
-    """The same volume from scipy's exact Euclidean transform (for volumes where the brute force is slow)."""
-    from scipy.ndimage import distance_transform_edt
-    o = np.asarray(occ, dtype=np.float64) > threshold
-    cap = cell * sum(o.shape)
-    if not o.any():
-        return np.full(o.shape, cap)
-    if o.all():
-        return np.full(o.shape, -cap)
-    # (squared integer distances back from the transform's doubles: exact below 2^53, so the one sqrt is the definition's)
-    d_out = np.rint(distance_transform_edt(~o) ** 2)
-    d_in = np.rint(distance_transform_edt(o) ** 2)
-    return np.where(o, -(np.sqrt(d_in) - 0.5) * cell, (np.sqrt(d_out) - 0.5) * cell)
+from tests.sdf_oracle import brute_sdf, scipy_sdf  # noqa: F401  (the transform: the tests reach it through this module)
 
 
 # ------------------------------------------------------------------------------------------------ the field
@@ -160,7 +120,15 @@ def mapping_volumes(tile_y=8):
     rng = np.random.default_rng(13)
     shapes = {"2x3x70": (2, 3, 70), "2x2x300": (2, 2, 300), "3x9x33": (3, tile_y + 1, 33), "9x3x5": (tile_y + 1, 3, 5),
               "1x1x130": (1, 1, 130), "130x1x1": (130, 1, 1), "1x70x1": (1, 70, 1)}
-    return {k: ((rng.uniform(size=s) < 0.08).astype(np.float64), 0.2) for k, s in shapes.items()}
+    out = {k: ((rng.uniform(size=s) < 0.08).astype(np.float64), 0.2) for k, s in shapes.items()}
+    # the one transform behind grid and volume: a squared distance of 99^2 = 9801, past the grid's sentinel of 8192, along each
+    # axis; and a line with no occupied cell at all (the cap)
+    for name, shape in (("100x1x1", (100, 1, 1)), ("1x100x1", (1, 100, 1)), ("1x1x100", (1, 1, 100))):
+        occ = np.zeros(shape)
+        occ.flat[0] = 1.
+        out[name] = (occ, 0.2)
+    out["1x1x100 all free"] = (np.zeros((1, 1, 100)), 0.2)
+    return out
 
 
 # The arm scene: 10 x 14 x 13 cells of 0.08 over x in [-0.4, 0.64), y in [-0.5, 0.62), z in [0, 0.8) -- the Panda and the toy
