@@ -1066,9 +1066,11 @@ extern "C" int sgpmp_update(sgpmp_ctx* c, const void* costs, int costs_dtype, co
     if (costs_dtype != SGPMP_F64 && costs_dtype != c->dims.dtype)
         return fail(SGPMP_EINVAL, "sgpmp_update: costs must be fp64 or the context dtype");
     if (!(temperature > 0.)) return fail(SGPMP_EINVAL, "sgpmp_update: temperature must be positive");
-    HIPCHK(launch_update(c->dims.dtype, c->dims.n_dof, c->dims.traj_len, c->dims.num_particles,
-                         c->dims.num_samples, costs, costs_dtype, samples, means, temperature, step_size,
-                         weights, grad, means_prev, stats, (hipStream_t)stream));
+    const UpdateShape shape = {c->dims.dtype, costs_dtype, c->dims.n_dof, c->dims.traj_len, c->dims.num_samples, c->dims.num_particles};
+    UpdateIo io = {};
+    io.costs = costs; io.samples = samples; io.means = means; io.temperature = temperature; io.step_size = step_size;
+    io.weights = weights; io.grad = grad; io.means_prev = means_prev; io.stats = stats; io.stream = (hipStream_t)stream;
+    HIPCHK(launch_update(plan_update(shape, update_wants(io), g_sgpmp_update_wide), io));
     return SGPMP_OK;
 }
 
@@ -1304,17 +1306,18 @@ static int run_range(sgpmp_ctx* c, const StepPlan& plan, const StepArgs& a, size
     HT(2);                                                       // the fused launch (or sampler + sweep)
     if (se) HIPCHK(hipEventRecord(se->ev[3], st));
     // (the update also prepares the NEXT step's importance-sampling weights -- unless, as a kernel of its own, the new
-    // means do not fit its LDS beside the weights: launch_update decides)
+    // means do not fit its LDS beside the weights: plan_update decides)
     *isw_written = plan.update_in_launch;
     if (plan.update_in_launch) {                                 // (fused_planar_seg.inc: seg_update)
         if (k4_done) HIPCHK(hipEventRecord(k4_done, st));
     } else {
-        const RegenHost regen = plan_regen(plan, pr, a.seed, a.draw, dense.store_threshold);
-        const EeFoldHost eeh = {eet, c->d_chain, cs};
-        HIPCHK(launch_update(D.dtype, D.n_dof, D.traj_len, P, S, c64, SGPMP_F64, X, mu, a.temperature, a.step_size, wh, gh, mph,
-                             slot, st, c->tg.comm_packet_event ? k4_done : nullptr, &pr, isw, isw_written, means_copy,
-                             plan.partials ? io.dense.part : nullptr, io.dense.nnz, dense.threshold,
-                             &regen, eet ? &eeh : nullptr));        // (recipe 0: nothing to regenerate; beside_chain all the same)
+        const UpdateIo uio = {c64, X, mu, a.temperature, a.step_size, wh, gh, mph, slot, st, c->tg.comm_packet_event ? k4_done : nullptr,
+                              &pr, isw, means_copy, plan.partials ? io.dense.part : nullptr, io.dense.nnz, dense.threshold,
+                              plan_regen(plan, pr, a.seed, a.draw, dense.store_threshold),   // (recipe 0: nothing to regenerate; beside_chain all the same)
+                              {eet, c->d_chain, cs}};
+        const UpdatePlan up = plan_update({D.dtype, SGPMP_F64, D.n_dof, D.traj_len, S, P}, update_wants(uio), g_sgpmp_update_wide);
+        HIPCHK(launch_update(up, uio));
+        *isw_written = up.tail && P > 0;
         if (!c->tg.comm_packet_event && k4_done) HIPCHK(hipEventRecord(k4_done, st));
         launches += 1;
     }

@@ -134,6 +134,24 @@ struct SgpmpToggles {
     long long k3_blocks;      // SGPMP_K3_BLOCKS            workgroup cap of the dual sweep (0: default)
 };
 
+// ---------------------------------------------------------------------------------- update_kernel's scratch
+// The dynamic LDS of one particle's update (update_common.h: update_particle), front to back, every region on 16 bytes:
+// S weights (double) + S indices (int) | the new means for the importance-sampling tail, M elements | the regeneration of a
+// store-free step (regen_lds_bytes) | the folded end-effector term, S doubles.  Kernels and host (update_plan.hip) read it here.
+// A workgroup's dynamic LDS at most, and the reserve for the kernels' static LDS.  The code objects say more than the reserve
+// (.group_segment_fixed_size, profiles/r14/update_plan.txt): update_kernel 1072 bytes with fp32 means and 1840 with fp64
+// (scratch[8], nnz_s, red3[12], ee_jr, ee_ji), update_kernel_quad 0.  Kept at its value: which shapes launch is behaviour.
+#define SGPMP_UPD_LDS_LIMIT 65536
+#define SGPMP_UPD_LDS_RESERVE 256
+constexpr size_t upd_lds_round(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+constexpr bool upd_lds_fits(size_t bytes) { return bytes + SGPMP_UPD_LDS_RESERVE <= SGPMP_UPD_LDS_LIMIT; }
+constexpr size_t upd_weights_bytes(int S) { return (size_t)S * 12; }
+constexpr size_t upd_means_offset(int S) { return upd_lds_round(upd_weights_bytes(S)); }
+// the regeneration: rows + tables + segment end states + (more rows with weight than one round holds) the carried sums
+constexpr size_t regen_lds_bytes(int recipe, int T, int n, int R) {
+    return (size_t)R * T * 2 * n * 4 + (size_t)T * 12 * 4 + (recipe == 2 ? (size_t)R * 16 * n * 2 * 4 : 0) + (size_t)T * 2 * n * 8;
+}
+
 #ifndef __HIPCC_RTC__     // host-side declarations: not part of the run-time (hiprtc) translation unit of chain_rtc.hip
 // ---------------------------------------------------------------------------------- collectives (comm.hip)
 // RCCL communicator of one context; every function returns NULL on success or a static error string.
@@ -248,17 +266,34 @@ struct RegenHost {
                                   // kernel launch_update takes; set with recipe 0 too)
 };
 // update_kernel_quad (update.hip): particles per workgroup, one wave each; the most samples and the range of particles of a
-// half's launch that takes it by default (update.hip: update_quad_applies has the measurements)
+// half's launch that takes it by default (update_plan.hip: update_quad_applies has the measurements)
 #define SGPMP_UPD_QUAD 4
 #define SGPMP_UPD_QUAD_MAX_S 256
 #define SGPMP_UPD_QUAD_MIN_P 512
 #define SGPMP_UPD_QUAD_END_P 1024
 // Development switch `update_wide` (sgpmp_set_option / SGPMP_UPDATE_WIDE): > 0: every update launch takes update_kernel (one
 // 256-thread workgroup per particle); < 0: update_kernel_quad wherever it can run, also where it is not the faster one; 0: the
-// measured rule.  PROCESS-WIDE, unlike the switches of SgpmpToggles: launch_update is handed no toggles, so the value lives here
+// measured rule.  PROCESS-WIDE, unlike the switches of SgpmpToggles: the callers of plan_update read it here
 // (one variable for the whole library: C++17 inline).  SGPMP_UPDATE_WIDE is read ONCE per process, by the first sgpmp_create;
 // after that only sgpmp_set_option changes it, for every context of the process.
 inline int g_sgpmp_update_wide = 0;
+
+// ---------------------------------------------------------------------------------- the update launch (update_plan.hip)
+// ONE decision per update launch, a function of its arguments alone (no HIP call): tail kept or dropped, the regions of the
+// kernel's scratch, one wave or one workgroup per particle, grid, vector width.
+struct UpdateShape { int dtype, costs_dtype, n, T, S, P; };
+// isw_tail: the next step's importance-sampling weights are wanted (written if the new means fit beside the weights);
+// regen_recipe, beside_chain: RegenHost's; ee_fold: EeFoldHost::term is there; has_nnz: the per-particle row counts are there
+struct UpdateWants { bool isw_tail; int regen_recipe; bool ee_fold; bool beside_chain; bool has_nnz; };
+struct UpdatePlan {
+    UpdateShape shape; bool ok;   // false: not this shape -- launch_update returns hipErrorInvalidValue
+    bool tail;                    // the kernel writes the next step's weights (what the step reports as prepared, when P > 0)
+    int regen_rows;               // RegenArgs::R
+    unsigned regen_off, ee_off;   // where the regeneration and the end-effector term's S doubles begin in a particle's scratch
+    unsigned slice, lds;          // one particle's scratch, rounded; dynamic LDS of the launch (quad: four slices)
+    bool quad; unsigned grid; int vw; const char* kernel;   // update_kernel_quad?  workgroups, elements per thread and load
+};
+UpdatePlan plan_update(const UpdateShape& shape, const UpdateWants& wants, int update_wide);
 int update_regen_rows(int dtype, int n, int T, int S, int recipe);   // rows per round update_kernel can regenerate; 0: not this shape
 bool update_ee_fold_fits(int dtype, int n, int T, int S);
 
@@ -329,13 +364,17 @@ hipError_t launch_is_weights(int dtype, int n, int T, const PriorDev& prior, con
                              int n_particles, double temperature, void* out, double* zero_stats,
                              hipStream_t stream);
 
-hipError_t launch_update(int dtype, int n, int T, int P, int S, const void* costs, int costs_dtype,
-                         const void* samples, void* means, double temperature, double step_size,
-                         void* weights, void* grad, void* means_prev, double* stats,
-                         hipStream_t stream, hipEvent_t done = nullptr, const PriorDev* isw_prior = nullptr,
-                         void* isw_next = nullptr, bool* isw_written = nullptr, void* means_copy = nullptr,
-                         const float* part = nullptr, unsigned* nnz = nullptr, unsigned nnz_threshold = 0,
-                         const RegenHost* regen = nullptr, const EeFoldHost* ee = nullptr);
+struct UpdateIo {                 // (everything behind `stream` may be null / zero; isw_prior and isw_next: both or neither)
+    const void* costs; const void* samples; void* means; double temperature, step_size;
+    void* weights; void* grad; void* means_prev; double* stats; hipStream_t stream; hipEvent_t done;
+    const PriorDev* isw_prior; void* isw_next; void* means_copy; const float* part; unsigned* nnz; unsigned nnz_threshold;
+    RegenHost regen; EeFoldHost ee;
+};
+static inline UpdateWants update_wants(const UpdateIo& io) {
+    return {io.isw_prior && io.isw_next, io.regen.recipe, io.ee.term != nullptr, io.regen.beside_chain != 0, io.nnz != nullptr};
+}
+// K4 (update.hip): enqueues exactly what the plan says; P <= 0 is a successful no-op
+hipError_t launch_update(const UpdatePlan& plan, const UpdateIo& io);
 
 hipError_t launch_stats_add(double* dst, const double* src, hipStream_t stream);
 hipError_t launch_mode_stats(int dtype, int n, int T, int P, long long p_offset, int nppg, int G, const void* means,

@@ -20,35 +20,13 @@
 #include "sgpmp_internal.h"
 #include "update_common.h"
 
-// LDS of update_kernel without the regeneration: weights + indices (+ the new means for the tail when they fit)
-static size_t update_base_lds(int dtype, int n, int T, int S) {
-    const size_t M = (size_t)T * 2 * n, lds = (size_t)S * (sizeof(double) + sizeof(int));
-    const size_t with_tail = ((lds + 15) & ~(size_t)15) + M * (dtype == SGPMP_F64 ? 8 : 4);
-    return with_tail + 256 <= 65536 ? with_tail : lds;
-}
-
-// Rows update_kernel can regenerate per round for this shape (4, 2, 1), or 0: a store-free step is not possible (the caller
-// then stores the samples as always).  fp32, M a multiple of 4 (16-byte elements), T even (a Philox block is two waypoints).
-int update_regen_rows(int dtype, int n, int T, int S, int recipe) {
-    if (dtype != SGPMP_F32 || (T * 2 * n) % 4 != 0 || T % 2 != 0 || recipe < 1 || recipe > 2) return 0;
-    const size_t base = (update_base_lds(dtype, n, T, S) + 15) & ~(size_t)15;
-    for (int R = 4; R >= 1; R >>= 1)
-        if (base + regen_lds_bytes(recipe, T, n, R) + 256 <= 65536) return R;
-    return 0;
-}
-
-// does update_kernel's scratch leave room for the folded end-effector term (S more doubles)?
-bool update_ee_fold_fits(int dtype, int n, int T, int S) {
-    return ((update_base_lds(dtype, n, T, S) + 15) & ~(size_t)15) + (size_t)S * sizeof(double) + 256 <= 65536;
-}
-
 // update_kernel with ONE WAVE per particle: wave w of workgroup b updates particle 4 b + w in its own slice of the dynamic
 // LDS (update_particle<.., 64>: no workgroup barrier, the four particles do not wait for each other), then ONE barrier and one
 // importance-sampling tail for the four particles with all 256 threads (is_weight_elem of the owning particle's means in
 // LDS: a pure function of (means, e), the bits of update_kernel's tail).  A quarter of update_kernel's waves: inside a
 // two-chain optimize() the update runs under the other chain's fused launch, where every wave waits for a slot, and its
 // duration there is serial in its own chain -- 55.9 -> 45.9 us per half at the headline shape (profiles/r12).
-// Storing steps without a folded end-effector term only (launch_update).
+// Storing steps without a folded end-effector term only (update_plan.hip: plan_update).
 template <typename real, typename cost_t, int VW>
 __global__ void __launch_bounds__(256)
 update_kernel_quad(int M, int S, int P, const cost_t* __restrict__ costs, const real* __restrict__ samples,
@@ -77,7 +55,7 @@ update_kernel_quad(int M, int S, int P, const cost_t* __restrict__ costs, const 
         __syncthreads();                                  // the new means of the workgroup's particles are in their slices
         const int Tn = M / nd, E = (Tn + 1) * nd;         // elements per particle; particle p0 + q owns [q E, (q + 1) E)
         const int live = P - p0 < SGPMP_UPD_QUAD ? P - p0 : SGPMP_UPD_QUAD;
-        const size_t mu_off = ((size_t)S * 12 + 15) & ~(size_t)15;
+        const size_t mu_off = upd_means_offset(S);
         real* out = nx.out + (size_t)p0 * E;
         for (int i = threadIdx.x; i < live * E; i += SGPMP_UPD_THREADS) {
             const int q = i / E, e = i - q * E;
@@ -88,110 +66,48 @@ update_kernel_quad(int M, int S, int P, const cost_t* __restrict__ costs, const 
     }
 }
 
-// Which launches take update_kernel_quad: a function of (S, P), the scratch size and what the launch is asked for, never of
-// timing.  It can run wherever nothing is regenerated, no end-effector term is folded in and four slices fit the workgroup's
-// LDS (the switch update_wide < 0 takes it there: tests, A/B).  It is TAKEN where it measured faster
-// (profiles/r12/update_quad_ab.txt and update_quad_rule_points.txt, same machine, alternating runs):
-//  * only for a half of a two-chain step (RegenHost::beside_chain).  Alone on the GPU it is the longer kernel -- a lane owns
-//    S / 64 costs and as many of the virtual waves' butterflies, one after the other: config 2 (planar 256 x 64 x 128, one
-//    chain) lost 10 .. 13 %, config 1 (planar 4 x 16 x 64 fp64) 3 .. 8 %, single-iteration calls at the headline shape
-//    (P = 1024, one chain) 1.0 .. 2.6 % with it.
-//  * SGPMP_UPD_QUAD_MIN_P = 512 <= P < SGPMP_UPD_QUAD_END_P = 1024 particles per half.  Against update_kernel, Panda T = 64,
-//    whole problem P x S: 1024 x 128 (the headline) +2.4 .. +3.2 %, 1024 x 64 +0.4 .. +3.2 %, 1024 x 256 +0.6 .. +1.6 %;
-//    512 x 128 (halves of 256) level inside 2 % of noise, config 5's share (512 x 256, T = 128) -1.3 .. -3.5 %;
-//    2048 x 128 (halves of 1024) -0.6, -0.9, +0.2 %.
-//  * S <= SGPMP_UPD_QUAD_MAX_S = 256, where the measurements end (+0.6 .. +1.6 % at 1024 x 256: four costs per lane).
-static bool update_quad_applies(int S, int P, size_t lds_one, bool regen, bool ee, bool beside_chain) {
-    if (g_sgpmp_update_wide > 0 || regen || ee) return false;
-    if (SGPMP_UPD_QUAD * ((lds_one + 15) & ~(size_t)15) + 256 > 65536) return false;
-    return g_sgpmp_update_wide < 0 || (beside_chain && S <= SGPMP_UPD_QUAD_MAX_S && P >= SGPMP_UPD_QUAD_MIN_P && P < SGPMP_UPD_QUAD_END_P);
+// One update launch: the tail's descriptor, the folded term, either kernel.  `done` (multi-GPU statistics): the event is signalled
+// by this kernel's own dispatch packet (hipExtLaunchKernelGGL stop event) instead of a separate barrier packet behind it
+template <typename real, typename cost_t, int VW>
+static void enqueue_update(const UpdatePlan& pl, const UpdateIo& io, const RegenArgs& rg) {
+    const int n = pl.shape.n, T = pl.shape.T, S = pl.shape.S, M = T * 2 * n;
+    const PriorDev* pr = pl.tail ? io.isw_prior : nullptr;
+    const IswNext<real> nx = {pr ? (real*)io.isw_next : nullptr, pr ? pr->Qinv : nullptr, pr ? pr->ks : 0., pr ? pr->kg : -1.,
+                              pr ? pr->dt : 0., n, pr ? pr->isotropic : 1};
+    const float* part = sizeof(real) == 4 && VW == 4 ? io.part : nullptr;
+    const dim3 grid(pl.grid), block(SGPMP_UPD_THREADS);
+    if (pl.quad) {
+        hipExtLaunchKernelGGL((update_kernel_quad<real, cost_t, VW>), grid, block, pl.lds, io.stream, (hipEvent_t) nullptr, io.done, 0u, M, S,
+                              pl.shape.P, (const cost_t*)io.costs, (const real*)io.samples, (real*)io.means, io.temperature, io.step_size,
+                              (real*)io.weights, (real*)io.grad, (real*)io.means_prev, io.stats, nx, (real*)io.means_copy, part, (S + 7) / 8,
+                              io.nnz, io.nnz_threshold, pl.slice);
+        return;
+    }
+    const EeFold<real> ee = io.ee.term ? EeFold<real>{io.ee.d_chain, make_ee_target<real>(*io.ee.term), n, T, (real*)io.ee.costs}
+                                       : EeFold<real>{nullptr, EeTarget<real>{}, n, T, nullptr};
+    hipExtLaunchKernelGGL((update_kernel<real, cost_t, VW>), grid, block, pl.lds, io.stream, (hipEvent_t) nullptr, io.done, 0u, M, S,
+                          (const cost_t*)io.costs, (const real*)io.samples, (real*)io.means, io.temperature, io.step_size, (real*)io.weights,
+                          (real*)io.grad, (real*)io.means_prev, io.stats, nx, (real*)io.means_copy, part, (S + 7) / 8, io.nnz,
+                          io.nnz_threshold, rg, pl.regen_off, ee, pl.ee_off);
 }
 
-hipError_t launch_update(int dtype, int n, int T, int P, int S, const void* costs, int costs_dtype,
-                         const void* samples, void* means, double temperature, double step_size,
-                         void* weights, void* grad, void* means_prev, double* stats,
-                         hipStream_t stream, hipEvent_t done, const PriorDev* isw_prior, void* isw_next,
-                         bool* isw_written, void* means_copy, const float* part, unsigned* nnz, unsigned nnz_threshold,
-                         const RegenHost* regen, const EeFoldHost* ee) {
-    const int M = T * 2 * n;
-    size_t lds = (size_t)S * (sizeof(double) + sizeof(int));
-    // (the softmax coefficients of the partials reuse the index array as doubles: 8 bytes per group of 8 rows fit its 4 S)
-    if (isw_prior) {
-        // + the new means for the tail.  Shapes whose weights fit the 64 KB of a workgroup but not together with
-        // the means (e.g. S = 4096, T = 512, n = 7 in fp32: 77 KB) run WITHOUT the tail: the next step then
-        // computes its importance-sampling weights with K5, as before the tail existed.
-        const size_t with_tail = ((lds + 15) & ~(size_t)15) + (size_t)M * (dtype == SGPMP_F64 ? 8 : 4);
-        if (with_tail + 256 <= 65536) lds = with_tail;
-        else isw_prior = nullptr;
-    }
-    const bool tail_fits = isw_prior != nullptr || isw_next == nullptr;
-    if (isw_written) *isw_written = isw_prior != nullptr && P > 0;
-    if (P <= 0) return hipSuccess;
+hipError_t launch_update(const UpdatePlan& pl, const UpdateIo& io) {
+    if (!pl.ok) return hipErrorInvalidValue;
+    if (pl.shape.P <= 0) return hipSuccess;
     // store-free step: the rows with weight are regenerated behind the kernel's usual scratch
     RegenArgs rg;
     std::memset(&rg, 0, sizeof(rg));
-    unsigned regen_off = 0;
-    if (regen && regen->recipe != 0) {
-        if (dtype != SGPMP_F32 || !nnz) return hipErrorInvalidValue;
-        const int R = update_regen_rows(dtype, n, T, S, regen->recipe);
-        if (R < 1) return hipErrorInvalidValue;                  // (the caller asked update_regen_rows before the launch that skipped the stores)
-        rg.recipe = regen->recipe; rg.N = n; rg.L = regen->L; rg.R = R; rg.seed = regen->seed; rg.draw = regen->draw;
-        rg.mode_offset = regen->mode_offset; rg.coef = regen->coef; rg.pre = regen->pre; rg.store_threshold = regen->store_threshold;
-        regen_off = (unsigned)((update_base_lds(dtype, n, T, S) + 15) & ~(size_t)15);
-        // (the scratch sized WITH the tail's means: without them the offset is merely generous)
-        if (lds < regen_off) lds = regen_off;
-        lds = regen_off + regen_lds_bytes(rg.recipe, T, n, R);
+    if (const RegenHost& r = io.regen; r.recipe != 0) {
+        rg.recipe = r.recipe; rg.N = pl.shape.n; rg.L = r.L; rg.R = pl.regen_rows; rg.seed = r.seed; rg.draw = r.draw;
+        rg.mode_offset = r.mode_offset; rg.coef = r.coef; rg.pre = r.pre; rg.store_threshold = r.store_threshold;
     }
-    // the step's end-effector goal term inside this kernel: S doubles behind everything else
-    unsigned ee_off = 0;
-    if (ee && ee->term) {
-        ee_off = (unsigned)((lds + 15) & ~(size_t)15);
-        lds = ee_off + (size_t)S * sizeof(double);
-        if (lds + 256 > 65536) return hipErrorInvalidValue;      // (the caller checks update_ee_fold_fits first)
-    }
-    dim3 grid(P), block(256);
-    const bool quad = tail_fits && update_quad_applies(S, P, lds, rg.recipe != 0, ee && ee->term, regen && regen->beside_chain);
-    const unsigned slice = (unsigned)((lds + 15) & ~(size_t)15);
-    if (quad) {
-        grid = dim3((P + SGPMP_UPD_QUAD - 1) / SGPMP_UPD_QUAD);
-        lds = (size_t)SGPMP_UPD_QUAD * slice;
-    }
-    // `done` (multi-GPU statistics): the event is signalled by this kernel's own dispatch packet
-    // (hipExtLaunchKernelGGL stop event) instead of a separate barrier packet behind it
-#define UPD(REAL, COST, VW)                                                                          \
-    hipExtLaunchKernelGGL((update_kernel<REAL, COST, VW>), grid, block, (unsigned)lds, stream, (hipEvent_t) nullptr, \
-                          done, 0u, M, S, (const COST*)costs, (const REAL*)samples, (REAL*)means, temperature, \
-                          step_size, (REAL*)weights, (REAL*)grad, (REAL*)means_prev, stats,          \
-                          IswNext<REAL>{isw_prior ? (REAL*)isw_next : nullptr, isw_prior ? isw_prior->Qinv : nullptr, \
-                                        isw_prior ? isw_prior->ks : 0., isw_prior ? isw_prior->kg : -1., \
-                                        isw_prior ? isw_prior->dt : 0., n, isw_prior ? isw_prior->isotropic : 1}, \
-                          (REAL*)means_copy, (dtype == SGPMP_F32 && M % 4 == 0) ? part : (const float*)nullptr, (S + 7) / 8, nnz, nnz_threshold, rg, regen_off, \
-                          (ee && ee->term) ? EeFold<REAL>{ee->d_chain, make_ee_target<REAL>(*ee->term), n, T, (REAL*)ee->costs} : EeFold<REAL>{nullptr, EeTarget<REAL>{}, n, T, nullptr}, ee_off)
-#define UPDQ(REAL, COST, VW)                                                                         \
-    hipExtLaunchKernelGGL((update_kernel_quad<REAL, COST, VW>), grid, block, (unsigned)lds, stream, (hipEvent_t) nullptr, \
-                          done, 0u, M, S, P, (const COST*)costs, (const REAL*)samples, (REAL*)means, temperature, \
-                          step_size, (REAL*)weights, (REAL*)grad, (REAL*)means_prev, stats,          \
-                          IswNext<REAL>{isw_prior ? (REAL*)isw_next : nullptr, isw_prior ? isw_prior->Qinv : nullptr, \
-                                        isw_prior ? isw_prior->ks : 0., isw_prior ? isw_prior->kg : -1., \
-                                        isw_prior ? isw_prior->dt : 0., n, isw_prior ? isw_prior->isotropic : 1}, \
-                          (REAL*)means_copy, (dtype == SGPMP_F32 && M % 4 == 0) ? part : (const float*)nullptr, (S + 7) / 8, nnz, nnz_threshold, slice)
-    if (quad) {
-        if (dtype == SGPMP_F64) {
-            if (M % 4 == 0) UPDQ(double, double, 4); else UPDQ(double, double, 2);
-        } else if (costs_dtype == SGPMP_F64) {
-            if (M % 4 == 0) UPDQ(float, double, 4); else UPDQ(float, double, 2);
-        } else {
-            if (M % 4 == 0) UPDQ(float, float, 4); else UPDQ(float, float, 2);
-        }
-    } else if (dtype == SGPMP_F64) {
-        if (M % 4 == 0) UPD(double, double, 4); else UPD(double, double, 2);
-    } else if (costs_dtype == SGPMP_F64) {
-        if (M % 4 == 0) UPD(float, double, 4); else UPD(float, double, 2);
-    } else {
-        if (M % 4 == 0) UPD(float, float, 4); else UPD(float, float, 2);
-    }
-#undef UPD
-#undef UPDQ
+    auto go = [&](auto real_tag, auto cost_tag) {
+        using real = decltype(real_tag); using cost_t = decltype(cost_tag);
+        if (pl.vw == 4) enqueue_update<real, cost_t, 4>(pl, io, rg); else enqueue_update<real, cost_t, 2>(pl, io, rg);
+    };
+    if (pl.shape.dtype == SGPMP_F64) go(double{}, double{});
+    else if (pl.shape.costs_dtype == SGPMP_F64) go(float{}, double{});
+    else go(float{}, float{});
     return hipGetLastError();
 }
 

@@ -282,15 +282,9 @@ __device__ __forceinline__ void regen_rows(const RegenArgs& rg, int T, unsigned 
     __syncthreads();
 }
 
-// LDS of the regeneration: rows + tables + segment end states + (more rows with weight than one round holds) the carried sums
-static inline size_t regen_lds_bytes(int recipe, int T, int n, int R) {
-    const size_t M = (size_t)T * 2 * n;
-    return (size_t)R * M * 4 + (size_t)T * 12 * 4 + (recipe == 2 ? (size_t)R * 16 * n * 2 * 4 : 0) + M * 8;
-}
-
 // The update of ONE particle by one 256-thread workgroup -- update_kernel's body.  `c`: the particle's S costs, `X`: its S
 // sample rows, `x_pitch` elements apart (global [S][M]), `lds_raw`: S * 12 (+ 16-byte round-up + M elements when nx.out)
-// bytes of workgroup scratch (+ regen_lds_bytes behind them when `regen`).  `stats` are ACCUMULATED into by atomics (shard p & 63).
+// bytes of workgroup scratch (+ regen_lds_bytes behind them when `regen`; sgpmp_internal.h has the layout).  `stats` are ACCUMULATED into by atomics (shard p & 63).
 // VW = elements per thread and load (4 when M % 4 == 0, else 2; M = T * 2n is always even).
 // regen: the particle's rows are NOT in memory (store-free step) -- the rows that carry weight are regenerated (rg says how).
 //
@@ -332,7 +326,7 @@ __device__ __forceinline__ void update_particle(int p, int M, int S, const cost_
     typedef real vec __attribute__((ext_vector_type(VW)));
     double* w = reinterpret_cast<double*>(lds_raw);                  // [S] weights
     int* idx = reinterpret_cast<int*>(lds_raw + (size_t)S * 8);      // [S] samples with weight != 0
-    real* mu_lds = reinterpret_cast<real*>(lds_raw + (((size_t)S * 12 + 15) & ~(size_t)15));   // [M] new means (tail)
+    real* mu_lds = reinterpret_cast<real*>(lds_raw + upd_means_offset(S));   // [M] new means (tail)
     __shared__ double scratch[8];
     __shared__ int nnz_s;
     const int tid = WAVE ? (int)(threadIdx.x & 63) : threadIdx.x < SGPMP_UPD_THREADS ? (int)threadIdx.x : 1 << 30;   // (extra threads: every loop is empty)

@@ -116,29 +116,29 @@ hipError_t launch_is_weights(int dtype, int n, int T, const PriorDev& p, const v
     wr(out, (size_t)P * (T + 1) * 2 * n * esz(dtype)); wr(zero_stats, sizeof(double) * SGPMP_STAT_SHARDS * 4);
     return hipSuccess;
 }
-hipError_t launch_update(int dtype, int n, int T, int P, int S, const void* costs, int cdt, const void* samples, void* means, double, double, void* weights,
-                         void* grad, void* means_prev, double* stats, hipStream_t, hipEvent_t done, const PriorDev* ip, void* isw_next, bool* isw_written,
-                         void* means_copy, const float* part, unsigned* nnz, unsigned, const RegenHost* regen, const EeFoldHost* ee) {
-    const size_t M = (size_t)T * 2 * n, w = esz(dtype);
-    rd(costs, (size_t)P * S * esz(cdt));
-    if (ee && ee->term) {                                      // the end-effector goal term inside the update: chain, rows, the cost output
-        rd(ee->d_chain, sizeof(ChainDev)); rd(samples, (size_t)P * S * M * w);
-        if (ee->costs) { rd(ee->costs, (size_t)P * S * w); wr(ee->costs, (size_t)P * S * w); }
+hipError_t launch_update(const UpdatePlan& plan, const UpdateIo& io) {
+    if (!plan.ok) return hipErrorInvalidValue;
+    const int n = plan.shape.n, T = plan.shape.T, P = plan.shape.P, S = plan.shape.S;
+    if (P <= 0) return hipSuccess;
+    const size_t M = (size_t)T * 2 * n, w = esz(plan.shape.dtype);
+    rd(io.costs, (size_t)P * S * esz(plan.shape.costs_dtype));
+    if (io.ee.term) {                                          // the end-effector goal term inside the update: chain, rows, the cost output
+        rd(io.ee.d_chain, sizeof(ChainDev)); rd(io.samples, (size_t)P * S * M * w);
+        if (io.ee.costs) { rd(io.ee.costs, (size_t)P * S * w); wr(io.ee.costs, (size_t)P * S * w); }
     }
-    if (regen && regen->recipe) {                              // store-free step: tables instead of rows
-        rd(regen->coef, sizeof(float) * T * 8);
-        if (regen->recipe == 2) rd(regen->pre, sizeof(float) * T * 4);
+    if (io.regen.recipe) {                                     // store-free step: tables instead of rows
+        rd(io.regen.coef, sizeof(float) * T * 8);
+        if (io.regen.recipe == 2) rd(io.regen.pre, sizeof(float) * T * 4);
     } else {
-        rd(samples, (size_t)P * S * M * w);
+        rd(io.samples, (size_t)P * S * M * w);
     }
-    wr(means, (size_t)P * M * w); wr(weights, (size_t)P * S * w); wr(grad, (size_t)P * M * w); wr(means_prev, (size_t)P * M * w);
-    wr(means_copy, (size_t)P * M * w);
-    if (stats) for (int i = 0; i < SGPMP_STAT_SHARDS * 4; ++i) stats[i] += 1.;        // accumulates, as the kernel's atomics do
-    if (ip) { rd(ip->Qinv, sizeof(double) * 4 * n * n); wr(isw_next, (size_t)P * (T + 1) * 2 * n * w); }
-    if (isw_written) *isw_written = ip != nullptr && P > 0;
-    if (part) rd(part, (size_t)P * (S / 8) * (M + 4) * 4);
-    if (nnz) { rd(nnz, (size_t)P * 4); wr(nnz, (size_t)P * 4, 1); }
-    if (done) return hipEventRecord(done, nullptr);
+    wr(io.means, (size_t)P * M * w); wr(io.weights, (size_t)P * S * w); wr(io.grad, (size_t)P * M * w); wr(io.means_prev, (size_t)P * M * w);
+    wr(io.means_copy, (size_t)P * M * w);
+    if (io.stats) for (int i = 0; i < SGPMP_STAT_SHARDS * 4; ++i) io.stats[i] += 1.;  // accumulates, as the kernel's atomics do
+    if (plan.tail) { rd(io.isw_prior->Qinv, sizeof(double) * 4 * n * n); wr(io.isw_next, (size_t)P * (T + 1) * 2 * n * w); }
+    if (io.part) rd(io.part, (size_t)P * (S / 8) * (M + 4) * 4);
+    if (io.nnz) { rd(io.nnz, (size_t)P * 4); wr(io.nnz, (size_t)P * 4, 1); }
+    if (io.done) return hipEventRecord(io.done, nullptr);
     return hipSuccess;
 }
 hipError_t launch_stats_add(double* dst, const double* src, hipStream_t) {

@@ -541,6 +541,27 @@ def test_step_plan_matches_its_table_under_sanitizers(tmp_path):
     shutil.rmtree(b, ignore_errors=True)
 
 
+def test_update_plan_matches_its_table_under_sanitizers(tmp_path):
+    """tests/host_asan/update_table.cpp: the REAL csrc/update_plan.hip (plan_update: the update launch's scratch layout, kernel,
+    grid and vector width; update_regen_rows and update_ee_fold_fits, which plan_step asks), compiled host-only with
+    -fsanitize=address,undefined, against a table recorded from the launcher it replaced -- and no two regions of a particle's
+    scratch may overlap or leave the launch's dynamic LDS."""
+    import shutil
+    import subprocess
+    if not os.path.exists("/opt/rocm/bin/hipcc") or not os.path.exists("/opt/rocm/lib/llvm/bin/clang++"):
+        pytest.skip("no ROCm clang")
+    d = os.path.join(ROOT, "tests", "host_asan")
+    b = str(tmp_path / "build")
+    r = subprocess.run(["make", "-C", d, f"B={b}", "-j4", os.path.join(b, "update_table")], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    env = {k: v for k, v in os.environ.items() if not k.startswith(("SGPMP_", "STUB_", "HOST_ASAN"))}
+    env["ASAN_OPTIONS"] = "detect_leaks=1:abort_on_error=0"
+    p = subprocess.run([os.path.join(b, "update_table")], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0 and "UPDATE_TABLE_OK" in p.stdout, (p.stdout[-1000:], p.stderr[-4000:])
+    assert "Sanitizer" not in p.stderr and "runtime error" not in p.stderr, p.stderr[-4000:]
+    shutil.rmtree(b, ignore_errors=True)
+
+
 def test_mirror_classes_accept_the_reference_signatures():
     """INTEGRATION.md section 1 says the classes of stoch_gpmp_amd keep the reference's names and signatures.  Checked against
     DATA dumped from the reference itself (oracle/gen_golden.py g11: inspect.signature of every public method of the classes

@@ -5,7 +5,8 @@ another path: two elements per thread (M % 4 != 0) in every dtype combination, S
 remainder) at chosen positions, P > 64 for the statistics shards; both K5 branches, with and without a goal, one and two
 blocks per particle; the statistics kernel's 16-wave round-robin, its unrolled loop, the count element alone in a block,
 shard offsets that cut a goal.  The bounds are derived from the kernels' arithmetic (fp64, except the fp32 subtraction
-x - mu and the final rounding of each output), not measured.  Needs the MI355X: run with `-m gpu`."""
+x - mu and the final rounding of each output), not measured.  Last, through Engine.step, the update whose scratch has no room
+for the importance-sampling tail.  Needs the MI355X: run with `-m gpu`."""
 import pytest
 import torch
 
@@ -221,3 +222,45 @@ def test_mode_stats_match_per_goal_fp64_sums(n, T, dtype):
             assert total[:, M, 0].tolist() == one[:, M, 0].tolist(), tag
             assert worst((total[:, :M] - one[:, :M]).abs(), 1e-13 * full_scale[:, :M]) <= 1, tag
     assert (3, 17, 51) in unsharded
+
+
+# ------------------------------------------------------------------------------------------ the step's update without its tail
+def two_steps(S, kept):
+    """Two sgpmp_step calls of a planar fp32 GP-cost problem, n = 2, T = 160, P = 2, S samples; the second with
+    SGPMP_STEP_MEANS_KEPT if `kept` -> (means, costs, statistics after each step, launches of the second step)."""
+    from stoch_gpmp_amd import _lib as L
+    n, T, P, dt = 2, 160, 2, 0.02
+    real, d = torch.float32, 2 * n
+    eng = engine(n, T, P, S, real)
+    try:
+        eng.set_prior(L.PRIOR_SAMPLE, dt, 1e-3, 20.0, 1e-3)
+        eng.set_costs([dict(kind=L.COST_GP, flags=0, sigma=20.0, dt=dt)])
+        means = U.isw_means((n, T, dt, 1e-3, 20.0, 1e-3), P, real).to(DEV)
+        out = []
+        for it in range(2):
+            samples, costs = torch.zeros(P, S, T, d, **TA(real)), torch.zeros(P, S, **TA(real))
+            stats = torch.zeros(64, 4, device=DEV, dtype=torch.float64)
+            eng.step(23, 2 + it, means, samples, 3.0, 0.5, costs=costs, stats=stats, flags=L.STEP_MEANS_KEPT if it and kept else 0)
+            torch.cuda.synchronize()
+            out += [means.clone().cpu(), costs.cpu(), stats.cpu()]
+        return out, eng.last_step_launches()
+    finally:
+        eng.close()
+
+
+def test_step_whose_update_has_no_room_for_the_tail_computes_the_next_weights_itself():
+    """Scratch of one particle's update, fp32, n = 2, T = 160: 12 S bytes of weights and indices, then the M * 4 = 2560 bytes of
+    new means the importance-sampling tail reads.  S = 5184: 62 208 + 2560 + the 256-byte reserve = 65 024 <= 65 536, the tail
+    runs and a step that keeps the means skips the weights launch.  S = 5248: 62 976 + 2560 + 256 = 65 792, the tail is
+    dropped (62 976 + update_kernel's 1072 bytes of static LDS = 64 048 still fit a workgroup): the update must say so, and
+    the next step must compute its weights with a launch of its own although told the means were kept -- everything it returns
+    equal, bit for bit, to the same two steps without the flag, with one launch more than at S = 5184."""
+    flagged, launches = two_steps(5248, True)
+    plain, launches_plain = two_steps(5248, False)
+    for i, (x, y) in enumerate(zip(flagged, plain)):
+        assert same_bits(x, y), i
+    assert bool(torch.isfinite(flagged[3]).all()) and not torch.equal(flagged[0], flagged[3])    # the second step moved the means
+    assert float(flagged[4].abs().max()) > 0 and float(flagged[5][:, 2].sum()) == 2
+    _, launches_tail = two_steps(5184, True)
+    assert launches == launches_tail + 1, (launches, launches_tail)
+    assert launches_plain == launches, (launches_plain, launches)
