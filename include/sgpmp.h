@@ -63,8 +63,10 @@ enum {
                                    (SE3_distance itself is third-party and un-vendored: DESIGN.md)      */
     SGPMP_COST_GRID_SDF = 7,    /* CostCollision + GridDistanceField: hinge on a signed-distance grid (no reference
                                    counterpart; defined at sgpmp_grid_sdf_build below)                   */
-    SGPMP_COST_VOXEL_SDF = 8    /* CostCollision + VoxelDistanceField: hinge on a voxel signed-distance field at the link
+    SGPMP_COST_VOXEL_SDF = 8,   /* CostCollision + VoxelDistanceField: hinge on a voxel signed-distance field at the link
                                    points (no reference counterpart; defined at sgpmp_voxel_sdf_build below) */
+    SGPMP_COST_BODY_SDF = 9     /* CostCollision + BodyDistanceField: the same hinge at the body's collision spheres, each with
+                                   its radius (no reference counterpart; defined at sgpmp_set_body below) */
 };
 enum { SGPMP_FIELD_RBF = 0, SGPMP_FIELD_SDF = 1, SGPMP_FIELD_OCCUPANCY = 2 };
 #define SGPMP_FLAG_GP_START 1      /* GP term includes the start-state unary factor (CostGP)  */
@@ -74,12 +76,14 @@ enum { SGPMP_FIELD_RBF = 0, SGPMP_FIELD_SDF = 1, SGPMP_FIELD_OCCUPANCY = 2 };
                                       the hinge and its gradient (GridDistanceField.compute_distance).  A query flag, not a cost:
                                       allowed only in a cost list whose single term is this one (else SGPMP_EINVAL), and the
                                       GPMP linearisation refuses a term that carries it.  VOXEL_SDF: the same query, min over
-                                      the link points of d and the gradient through the first arg-min point */
+                                      the link points of d and the gradient through the first arg-min point.  BODY_SDF: min over
+                                      the body's spheres of the clearance d - r and the gradient through the first arg-min sphere */
 
 #define SGPMP_MAX_TERMS 8
 #define SGPMP_MAX_JOINTS 16
 #define SGPMP_MAX_DOF 8            /* state blocks are handled as one 16x16 MFMA tile        */
 #define SGPMP_MAX_INTERP 8
+#define SGPMP_MAX_BODY 64          /* collision spheres of a body (sgpmp_set_body)           */
 #define SGPMP_STAT_SHARDS 64       /* statistics buffers are double[SGPMP_STAT_SHARDS][4]; sum over shards */
 
 typedef struct sgpmp_dims {
@@ -546,6 +550,42 @@ int sgpmp_grid_sdf_build(sgpmp_ctx* ctx, const void* occ, int ny, int nx, double
  * sgpmp_validate refuse a cost list that holds the term (SGPMP_EINVAL): their kernels do not evaluate it. */
 int sgpmp_voxel_sdf_build(sgpmp_ctx* ctx, const void* occ, int nz, int ny, int nx, double cell, double threshold, void* sdf,
                           void* stream);
+
+/* ---- body collision spheres on the voxel field (SGPMP_COST_BODY_SDF) -----------------------------
+ * The robot side of the voxel field above: instead of the link origins, the term evaluates a BODY, a table of M spheres fixed in
+ * the link frames, 1 <= M <= SGPMP_MAX_BODY.  Sphere m has a link index l_m, a centre c_m in that link's frame and a radius
+ * r_m >= 0.  Link frames are sgpmp_fk's: frame 0 is the base, frame j + 1 follows joint j, its rotation included, so
+ * 0 <= l_m <= n_joints.  No reference counterpart.
+ *
+ * sgpmp_set_body: links HOST int32[n] in non-decreasing order, spheres HOST double[n][4] = (cx, cy, cz, r); uploaded in the ctx
+ * dtype; one body per context; n = 0 clears it.  SGPMP_EINVAL: n outside [0, 64], a null table with n > 0, links not in
+ * non-decreasing order, a negative or non-finite radius, a non-finite centre, a link index past the chain's last frame;
+ * SGPMP_ESTATE: no FK chain.  A later sgpmp_set_fk clears the body.  Synchronous.
+ *
+ * The term: sgpmp_cost_desc packed exactly as SGPMP_COST_VOXEL_SDF's (data = sdf volume, reserved / dim0 / dim1 = nz / ny / nx,
+ * p0 / p1 / p2 / dt = cell and the three offsets, sigma -> K = 1 / sigma^2, sigma2 = margin >= 0); num_interpolate must be 0
+ * (SGPMP_EINVAL).  With (R_l, P_l) the frame of link l at configuration q and d(.) the trilinear signed distance of
+ * SGPMP_COST_VOXEL_SDF (the same device function, the same clamping, the same NaN rule):
+ *   p_m(q) = P_l + R_l c_m                       world centre
+ *   s_m = d(p_m) - r_m                           clearance
+ *   h_m = (margin + r_m) - d(p_m) where that is > 0, else 0      (the hinge on margin - s_m)
+ *   f(q) = sum over m of h_m, in table order;  the term in a cost list is K * sum over t = 1 .. T-1 of f(q_t).
+ * Gradient, with g_m = dh_m/dp (-grad d where h_m > 0, exactly 0 elsewhere): df/dq_j = sum over the spheres on links behind
+ * revolute joint j of z_j . ((p_m - o_j) x g_m) -- sgpmp_field_grad's recurrence z_j . (M_j - o_j x F_j), which holds for any point
+ * rigidly attached behind the joint.  Spheres on link 0 contribute to the value and never to the gradient.  A non-finite
+ * coordinate of a sphere centre gives NaN in the value and in EVERY gradient entry.
+ * A program that holds the term without a body fails with SGPMP_ESTATE and a message that names sgpmp_set_body, whatever the
+ * call order (the body may be set before or after sgpmp_set_costs).
+ * Consumers: sgpmp_cost_eval / sgpmp_step / sgpmp_optimize (sampler + generic sweep + body_cost_kernel + update: the sweep skips
+ * the term, body_cost_kernel adds it to the costs behind it on the same stream -- one wave per trajectory, lane = waypoint, one
+ * writer per cost element, no atomics; no fused launch takes the term), sgpmp_field_eval on explicit frames [B, L, 4, 4] (the
+ * frames carry the rotations; L must exceed the body's last link index), sgpmp_field_grad, and one of the four field slots of
+ * sgpmp_gpmp_linearize (with and without sgpmp_gpmp_set_dense).  With SGPMP_FLAG_GRID_DISTANCE sgpmp_field_grad returns
+ * min over m of s_m and the gradient through the FIRST arg-min sphere (table order, strict comparison): a query, allowed only as
+ * the cost list's single term (else SGPMP_EINVAL) and refused by GPMP.  sgpmp_dense_cost, sgpmp_dense_cost_grad and
+ * sgpmp_validate refuse a cost list that holds the term (SGPMP_EINVAL): their kernels do not evaluate it.  SGPMP_ESTATE from
+ * sgpmp_set_costs in a build without the kernels (csrc/body_sdf.hip). */
+int sgpmp_set_body(sgpmp_ctx* ctx, const int32_t* links, const double* spheres, int n);
 
 /* trajs [B,T,d] -> out [B,T_f,d], ctx dtype, T = dims.traj_len. */
 int sgpmp_interpolate(sgpmp_ctx* ctx, const void* trajs, int64_t batch, int n_sub, double dt, void* out, void* stream);

@@ -107,6 +107,11 @@ struct sgpmp_ctx {
     hipEvent_t k1_fork = nullptr;
     // link pairs (i, j), i - j >= 2, whose distance depends on q: bit j of word i (sgpmp_validate's self-clearance column)
     uint32_t pair_mask[SGPMP_MAX_LINKS] = {};
+    // the body of SGPMP_COST_BODY_SDF (sgpmp_set_body): DEVICE int32 link[SGPMP_MAX_BODY], then [SGPMP_MAX_BODY][4] centre and
+    // radius in the ctx dtype; allocated by the first sgpmp_set_body
+    void* d_body = nullptr;
+    int n_body = 0;                  // 0: no body
+    int body_last_link = 0;          // the largest link index of the table
 };
 
 // name -> field of SgpmpToggles (environment variable = "SGPMP_" + upper-case name)
@@ -384,7 +389,7 @@ extern "C" void sgpmp_destroy(sgpmp_ctx* c) {
     free_prior(c->prior[1]);
     hipFree(c->d_qc); hipFree(c->d_prog); hipFree(c->d_chain); hipFree(c->d_isw);
     hipFree(c->d_costs64); hipFree(c->d_done); hipFree(c->d_tail_acc);
-    hipFree(c->d_part); hipFree(c->d_nnz);
+    hipFree(c->d_part); hipFree(c->d_nnz); hipFree(c->d_body);
     if (c->ms_side) { hipStreamSynchronize(c->ms_side); hipStreamDestroy(c->ms_side); }
     for (int i = 0; i < 2; ++i) { hipFree(c->ms_snap[i]); if (c->ms_read[i]) hipEventDestroy(c->ms_read[i]); }
     if (c->ms_ready) hipEventDestroy(c->ms_ready);
@@ -716,6 +721,28 @@ extern "C" int sgpmp_set_costs(sgpmp_ctx* c, const sgpmp_cost_desc* descs, int n
                 t.K2 = s.sigma2;                                  // the hinge's margin (TermK::K2)
                 prog.needs_fk = 1;
                 break;
+            case SGPMP_COST_BODY_SDF:
+                // packed exactly as SGPMP_COST_VOXEL_SDF; the spheres come from sgpmp_set_body (finalize_program joins the two).  Not
+                // a field of the sweep: needs_fk stays as the other terms leave it, body_cost_kernel walks the chain itself
+                if (!launch_body_cost || !launch_body_grad || !launch_body_eval)
+                    return fail(SGPMP_ESTATE, "sgpmp_set_costs: this build has no body_sdf kernels (SGPMP_COST_BODY_SDF)");
+                if (!s.data || s.reserved < 1 || s.dim0 < 1 || s.dim1 < 1 || !(s.p0 > 0.) || !(s.sigma2 >= 0.))
+                    return fail(SGPMP_EINVAL, "sgpmp_set_costs: body distance term needs a device sdf volume, cell size and margin >= 0");
+                if (c->dims.n_dof < 1)
+                    return fail(SGPMP_EINVAL, "sgpmp_set_costs: body distance term needs n_dof >= 1");
+                if ((s.flags & SGPMP_FLAG_GRID_DISTANCE) && n_desc != 1)
+                    return fail(SGPMP_EINVAL, "sgpmp_set_costs: SGPMP_FLAG_GRID_DISTANCE is a query flag for sgpmp_field_grad: "
+                                              "the term must be the cost list's only one");
+                if (s.num_interpolate != 0)
+                    return fail(SGPMP_EINVAL, "sgpmp_set_costs: body distance term takes no interpolated points (num_interpolate must be 0)");
+                t.dev_data = s.data;
+                t.dim0 = s.dim0; t.dim1 = s.dim1;
+                t.rows_per_goal = s.reserved;                     // nz (TermK::rows_per_goal)
+                t.inv_cell = 1. / s.p0;
+                t.off_x = s.p1; t.off_y = s.p2;
+                t.dt = s.dt;                                      // the z offset (TermK::dt)
+                t.K2 = s.sigma2;                                  // the hinge's margin (TermK::K2)
+                break;
             case SGPMP_COST_SPHERES:
             case SGPMP_COST_SELF:
                 if (s.num_interpolate < 0 || s.num_interpolate > SGPMP_MAX_INTERP)
@@ -906,6 +933,41 @@ extern "C" int sgpmp_set_fk(sgpmp_ctx* c, const sgpmp_joint* chain, int n_joints
     HIPCHK(hipMemcpy(c->d_chain, &ch, sizeof(ch), hipMemcpyHostToDevice));
     c->have_chain = true;
     c->prog_dirty = true;
+    c->n_body = 0;                                               // the body's link indices belonged to the old chain
+    return SGPMP_OK;
+}
+
+// The body of SGPMP_COST_BODY_SDF (include/sgpmp.h): checked on the host, uploaded in the ctx dtype.  One body per context.
+extern "C" int sgpmp_set_body(sgpmp_ctx* c, const int32_t* links, const double* spheres, int n) {
+    if (!c) return fail(SGPMP_EINVAL, "sgpmp_set_body: null context");
+    if (n < 0 || n > SGPMP_MAX_BODY) return fail(SGPMP_EINVAL, "sgpmp_set_body: the body has 0 (clear) to 64 spheres");
+    if (n > 0 && (!links || !spheres)) return fail(SGPMP_EINVAL, "sgpmp_set_body: null table");
+    for (int m = 0; m < n; ++m) {
+        if (links[m] < 0 || (m > 0 && links[m] < links[m - 1]))
+            return fail(SGPMP_EINVAL, "sgpmp_set_body: link indices must be >= 0 and in non-decreasing order");
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(spheres[m * 4 + k])) return fail(SGPMP_EINVAL, "sgpmp_set_body: non-finite sphere centre");
+        if (!std::isfinite(spheres[m * 4 + 3]) || spheres[m * 4 + 3] < 0.)
+            return fail(SGPMP_EINVAL, "sgpmp_set_body: a radius must be finite and >= 0");
+    }
+    if (!c->have_chain) return fail(SGPMP_ESTATE, "sgpmp_set_body: no FK chain (sgpmp_set_fk first)");
+    if (n > 0 && links[n - 1] > c->h_chain.n_joints)
+        return fail(SGPMP_EINVAL, "sgpmp_set_body: link index past the chain's last frame");
+    c->prog_dirty = true;
+    c->n_body = 0;
+    if (n == 0) return SGPMP_OK;
+    const size_t link_bytes = SGPMP_MAX_BODY * sizeof(int32_t), bytes = link_bytes + (size_t)SGPMP_MAX_BODY * 4 * c->esz;
+    std::vector<unsigned char> host(bytes, 0);
+    std::memcpy(host.data(), links, (size_t)n * sizeof(int32_t));
+    for (int i = 0; i < n * 4; ++i) {
+        if (c->dims.dtype == SGPMP_F64) reinterpret_cast<double*>(host.data() + link_bytes)[i] = spheres[i];
+        else reinterpret_cast<float*>(host.data() + link_bytes)[i] = (float)spheres[i];
+    }
+    HIPCHK(hipDeviceSynchronize());                              // (a launch in flight may still read the old table)
+    if (!c->d_body) HIPCHK(hipMalloc(&c->d_body, bytes));
+    HIPCHK(hipMemcpy(c->d_body, host.data(), bytes, hipMemcpyHostToDevice));
+    c->n_body = n;
+    c->body_last_link = links[n - 1];
     return SGPMP_OK;
 }
 
@@ -966,6 +1028,14 @@ static int finalize_program(sgpmp_ctx* c) {
         return fail(SGPMP_ESTATE, "link-distance / end-effector cost terms need an FK chain (sgpmp_set_fk)");
     for (int i = 0; i < p.n_terms; ++i) {
         CostTerm& t = p.terms[i];
+        if (t.kind == SGPMP_COST_BODY_SDF) {       // the term and the context's body meet here, whichever was set first
+            if (!c->have_chain || c->n_body < 1)
+                return fail(SGPMP_ESTATE, "the body distance term (SGPMP_COST_BODY_SDF) needs an FK chain and a body: "
+                                          "sgpmp_set_fk, then sgpmp_set_body");
+            t.body = c->d_body;
+            t.n_body = c->n_body;
+            continue;
+        }
         if (t.kind != SGPMP_COST_SPHERES && t.kind != SGPMP_COST_SELF && t.kind != SGPMP_COST_VOXEL_SDF) continue;
         const int L = c->h_chain.n_links;
         int extra = 0;
@@ -1302,6 +1372,8 @@ static int run_range(sgpmp_ctx* c, const StepPlan& plan, const StepArgs& a, size
                            (long long)plan.shape.offset * S, a.spheres, a.n_spheres, isw, S, pr.dt, cs, c64, st, c->tg,
                            &c->last_cost_kernel));
         launches += 2;
+        for (int i = 0; i < c->h_prog.n_terms; ++i)                 // (body_cost_kernel behind the sweep, once per body term)
+            if (c->h_prog.terms[i].kind == SGPMP_COST_BODY_SDF) launches += 1;
     }
     HT(2);                                                       // the fused launch (or sampler + sweep)
     if (se) HIPCHK(hipEventRecord(se->ev[3], st));
@@ -1557,6 +1629,14 @@ extern "C" int sgpmp_field_eval(sgpmp_ctx* c, int term, const void* frames, int6
         return fail(SGPMP_EINVAL, "sgpmp_field_eval: bad argument");
     if (!c->have_costs || term < 0 || term >= c->h_prog.n_terms)
         return fail(SGPMP_EINVAL, "sgpmp_field_eval: bad term index");
+    if (c->h_prog.terms[term].kind == SGPMP_COST_BODY_SDF) {     // the body's spheres in the given frames (they carry the rotations)
+        int rc;
+        if ((rc = finalize_program(c)) != SGPMP_OK) return rc;
+        if (n_links <= c->body_last_link)
+            return fail(SGPMP_EINVAL, "sgpmp_field_eval: the body has a sphere on a link past the given frames");
+        HIPCHK(launch_body_eval(c->dims.dtype, c->h_prog.terms[term], frames, batch, n_links, out, (hipStream_t)stream));
+        return SGPMP_OK;
+    }
     CostTerm t = c->h_prog.terms[term];
     if (t.kind != SGPMP_COST_SPHERES && t.kind != SGPMP_COST_SELF && t.kind != SGPMP_COST_EE_GOAL &&
         t.kind != SGPMP_COST_VOXEL_SDF)
@@ -1594,6 +1674,8 @@ static int term_value_grad(sgpmp_ctx* c, const CostTerm& t, const void* q, long 
     const int dtype = c->dims.dtype, n = c->dims.n_dof;
     if (t.kind == SGPMP_COST_GRID_SDF) {                  // a field of the planar point itself: no FK chain
         HIPCHK(launch_grid_sdf_grad(dtype, n, t, q, batch, traj_T, value, grad, st));
+    } else if (t.kind == SGPMP_COST_BODY_SDF) {           // the body's spheres: a walk of its own (body_sdf.hip)
+        HIPCHK(launch_body_grad(dtype, n, t, c->d_chain, c->h_chain.n_joints, q, batch, traj_T, value, grad, st));
     } else if (t.kind != SGPMP_COST_EE_GOAL) {
         HIPCHK(launch_field_grad(dtype, n, t, c->d_chain, c->h_chain.n_joints, q, batch, traj_T, spheres, n_spheres, value,
                                  grad, st));
@@ -1619,6 +1701,8 @@ extern "C" int sgpmp_field_grad(sgpmp_ctx* c, int term, const void* q, int64_t b
     } else {
         if (c->h_prog.terms[term].kind == SGPMP_COST_VOXEL_SDF && !c->have_chain)
             return fail(SGPMP_ESTATE, "sgpmp_field_grad: the voxel distance term needs an FK chain (sgpmp_set_fk)");
+        if (c->h_prog.terms[term].kind == SGPMP_COST_BODY_SDF && !c->have_chain)
+            return fail(SGPMP_ESTATE, "sgpmp_field_grad: the body distance term needs an FK chain and a body (sgpmp_set_fk, sgpmp_set_body)");
         if (!c->have_chain) return fail(SGPMP_EINVAL, "sgpmp_field_grad: no FK chain (sgpmp_set_fk)");
         int rc;
         if ((rc = finalize_program(c)) != SGPMP_OK) return rc;
@@ -1627,7 +1711,8 @@ extern "C" int sgpmp_field_grad(sgpmp_ctx* c, int term, const void* q, int64_t b
             if ((t.flags & 15) == SGPMP_FIELD_OCCUPANCY)
                 return fail(SGPMP_EINVAL, "sgpmp_field_grad: the occupancy count has no gradient (rbf and sdf sphere fields do)");
             if (!spheres || n_spheres < 1) return fail(SGPMP_EINVAL, "LinkDistanceField cost needs obstacle_spheres");
-        } else if (t.kind != SGPMP_COST_EE_GOAL && t.kind != SGPMP_COST_SELF && t.kind != SGPMP_COST_VOXEL_SDF) {
+        } else if (t.kind != SGPMP_COST_EE_GOAL && t.kind != SGPMP_COST_SELF && t.kind != SGPMP_COST_VOXEL_SDF &&
+                   t.kind != SGPMP_COST_BODY_SDF) {
             return fail(SGPMP_EINVAL, "sgpmp_field_grad: term is not a smooth link field");
         }
         if (t.kind != SGPMP_COST_EE_GOAL && t.n_points > SGPMP_MAX_POINTS)
@@ -1664,11 +1749,15 @@ static int gpmp_args(sgpmp_ctx* c, GpmpArgs& a, int* field_terms) {
             case SGPMP_COST_EE_GOAL:                      // (a field row on the last waypoint only)
             case SGPMP_COST_SELF:
             case SGPMP_COST_VOXEL_SDF:                    // (a link field like SPHERES: launch_field_grad)
+            case SGPMP_COST_BODY_SDF:                     // (the body's spheres: launch_body_grad)
             case SGPMP_COST_GRID_SDF:                     // (a field of the planar point: no FK chain)
-                if ((t.kind == SGPMP_COST_GRID_SDF || t.kind == SGPMP_COST_VOXEL_SDF) && (t.flags & SGPMP_FLAG_GRID_DISTANCE))
+                if ((t.kind == SGPMP_COST_GRID_SDF || t.kind == SGPMP_COST_VOXEL_SDF || t.kind == SGPMP_COST_BODY_SDF) &&
+                    (t.flags & SGPMP_FLAG_GRID_DISTANCE))
                     return fail(SGPMP_EINVAL, t.kind == SGPMP_COST_GRID_SDF
                         ? "GPMP: a grid distance term with SGPMP_FLAG_GRID_DISTANCE is a query, not a cost"
-                        : "GPMP: a voxel distance term with SGPMP_FLAG_GRID_DISTANCE is a query, not a cost");
+                        : t.kind == SGPMP_COST_VOXEL_SDF
+                        ? "GPMP: a voxel distance term with SGPMP_FLAG_GRID_DISTANCE is a query, not a cost"
+                        : "GPMP: a body distance term with SGPMP_FLAG_GRID_DISTANCE is a query, not a cost");
                 if (a.n_fields == 4) return fail(SGPMP_EINVAL, "GPMP: more than 4 link-field terms");
                 field_terms[a.n_fields] = i;
                 a.f[a.n_fields].K = t.K;

@@ -370,6 +370,24 @@ static hipError_t cost_dispatch(int n, int T, const CostProgram& h_prog, const C
     return hipGetLastError();
 }
 
+// What sgpmp_last_cost_kernel reports for a sweep with body_cost_kernel behind it.  A program that holds the body term is never
+// FLAT, so the sweep is one of cost_dispatch's four non-FLAT forms, in either dtype.
+static const char* body_sweep_name(const char* sweep) {
+    static const char* const names[][2] = {
+        {"cost_sweep_kernel<f32, generated chain>", "cost_sweep_kernel<f32, generated chain> + body_cost_kernel"},
+        {"cost_sweep_kernel<f64, generated chain>", "cost_sweep_kernel<f64, generated chain> + body_cost_kernel"},
+        {"cost_sweep_kernel<f32, register FK>", "cost_sweep_kernel<f32, register FK> + body_cost_kernel"},
+        {"cost_sweep_kernel<f64, register FK>", "cost_sweep_kernel<f64, register FK> + body_cost_kernel"},
+        {"cost_sweep_kernel<f32, generic FK>", "cost_sweep_kernel<f32, generic FK> + body_cost_kernel"},
+        {"cost_sweep_kernel<f64, generic FK>", "cost_sweep_kernel<f64, generic FK> + body_cost_kernel"},
+        {"cost_sweep_kernel<f32, no FK>", "cost_sweep_kernel<f32, no FK> + body_cost_kernel"},
+        {"cost_sweep_kernel<f64, no FK>", "cost_sweep_kernel<f64, no FK> + body_cost_kernel"},
+    };
+    for (const auto& n : names)
+        if (std::strcmp(sweep, n[0]) == 0 || std::strcmp(sweep, n[1]) == 0) return n[1];
+    return "cost sweep + body_cost_kernel";
+}
+
 hipError_t launch_cost(int dtype, int n, int T, const CostProgram& h_prog, const ChainDev* d_chain,
                        const ChainDev& h_chain, const void* trajs, long long batch,
                        long long batch_offset, const void* spheres, int n_spheres,
@@ -390,6 +408,14 @@ hipError_t launch_cost(int dtype, int n, int T, const CostProgram& h_prog, const
     for (int i = 0; i < h_prog.n_terms && e == hipSuccess; ++i)
         if (h_prog.terms[i].kind == SGPMP_COST_EE_GOAL)
             e = launch_ee_goal(dtype, n, T, h_prog.terms[i], d_chain, trajs, batch, costs, costs64, stream);
+    // body collision spheres (SGPMP_COST_BODY_SDF): the sweep skips the kind; body_cost_kernel (body_sdf.hip) adds the term to
+    // the costs in the same way, one wave per trajectory
+    for (int i = 0; i < h_prog.n_terms && e == hipSuccess; ++i)
+        if (h_prog.terms[i].kind == SGPMP_COST_BODY_SDF) {
+            if (!launch_body_cost) return hipErrorInvalidValue;      // (a build without body_sdf.hip: sgpmp_set_costs has refused)
+            e = launch_body_cost(dtype, n, T, h_prog.terms[i], d_chain, trajs, batch, costs, costs64, stream);
+            if (e == hipSuccess && picked) *picked = body_sweep_name(*picked);
+        }
     return e;
 }
 

@@ -60,6 +60,8 @@ struct CostTerm {
     double alpha[SGPMP_MAX_INTERP];
     double target[16];    // EE_GOAL: target end-effector frame
     double w_pos, w_rot;  // EE_GOAL
+    const void* body;     // BODY_SDF: the context's body table (DEVICE: int32 link[SGPMP_MAX_BODY], then [SGPMP_MAX_BODY][4] centre
+    int n_body;           // and radius in the ctx dtype) and its sphere count; filled by finalize_program, host use only
 };
 
 struct CostProgram {
@@ -450,6 +452,16 @@ hipError_t launch_gpmp_dense_solve(int dtype, const GpmpArgs& a, const GpmpDense
 // Weak for the same reason: sgpmp_field_grad and the GPMP linearisation refuse the kind where the definition is absent.
 hipError_t launch_grid_sdf_grad(int dtype, int n, const CostTerm& term, const void* q, long long batch, int traj_T, void* value,
                                 void* grad, hipStream_t stream) __attribute__((weak));
+// SGPMP_COST_BODY_SDF (body_sdf.hip; term.body / term.n_body: the table): body_cost_kernel adds K * sum over waypoints 1 .. T-1 of the
+// field to costs / costs64 [batch] behind the sweep; body_grad_kernel: value [batch] and gradient [batch, n], q laid out as
+// launch_field_grad's, the query flag included; body_eval_kernel: frames [batch, n_links, 4, 4] -> the field [batch].  Weak for
+// the same reason: sgpmp_set_costs refuses the kind where the definitions are absent.
+hipError_t launch_body_cost(int dtype, int n, int T, const CostTerm& term, const ChainDev* d_chain, const void* trajs,
+                            long long batch, void* costs, double* costs64, hipStream_t stream) __attribute__((weak));
+hipError_t launch_body_grad(int dtype, int n, const CostTerm& term, const ChainDev* d_chain, int n_joints, const void* q,
+                            long long batch, int traj_T, void* value, void* grad, hipStream_t stream) __attribute__((weak));
+hipError_t launch_body_eval(int dtype, const CostTerm& term, const void* frames, long long batch, int n_links, void* out,
+                            hipStream_t stream) __attribute__((weak));
 hipError_t launch_link_dist(int dtype, const void* frames, long long batch, int n_links, const void* spheres,
                             int n_other, int mode, double buffer, void* out, hipStream_t stream);
 hipError_t launch_fk(int dtype, int n, const ChainDev* d_chain, int n_links, const void* q,

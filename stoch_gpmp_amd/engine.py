@@ -290,6 +290,11 @@ class Engine:
 
     def set_costs(self, descs):
         """descs: list of dicts produced by the Cost classes' `descriptor()`."""
+        bodies = [dsc["body"] for dsc in descs if dsc.get("body") is not None]
+        if any(b != bodies[0] for b in bodies[1:]):
+            raise ValueError("Engine.set_costs: two different bodies in one cost list (a context holds one body)")
+        if bodies:                                      # (before the program: sgpmp_set_costs itself does not need it yet)
+            self.set_body(bodies[0])
         arr = (L.CostDesc * max(len(descs), 1))()
         self._keep = []
         host_keep = []
@@ -343,6 +348,17 @@ class Engine:
                 self.fk_codegen_error = str(e)
                 import warnings
                 warnings.warn(f"stoch_gpmp_amd: no run-time chain code for this robot ({e}); using the generic cost sweep")
+
+    def set_body(self, body):
+        """The collision spheres of SGPMP_COST_BODY_SDF (robots/body.py: BodySpheres, or None to clear): sgpmp_set_body.  Needs
+        the FK chain (set_fk first); a later set_fk clears the body."""
+        n = 0 if body is None else len(body)
+        links = (C.c_int32 * max(n, 1))(*([int(v) for v in body.links] if n else [0]))
+        flat = [float(v) for row in body.table() for v in row] if n else [0.] * 4
+        sph = (C.c_double * len(flat))(*flat)
+        with torch.cuda.device(self.device):
+            L.check(self.lib.sgpmp_set_body(self._ctx, links, sph, n))
+        self.body = body if n else None
 
     def fk_codegen_info(self):
         """(codegen_id, seconds in hiprtc, code objects compiled, taken from the disk cache); codegen_id: 0 run-time

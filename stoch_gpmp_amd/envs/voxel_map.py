@@ -78,6 +78,10 @@ class VoxelMap:
         """The smooth collision field of this volume: VoxelDistanceField(self, margin, threshold, ...)."""
         return VoxelDistanceField(self, margin, threshold=threshold, **kwargs)
 
+    def body_field(self, body, margin, threshold=0., **kwargs):
+        """The same field evaluated at a body's collision spheres (robots/body.py): BodyDistanceField(self, body, margin, ...)."""
+        return BodyDistanceField(self, body, margin, threshold=threshold, **kwargs)
+
 
 class VoxelDistanceField(DeviceSdf, DistanceField):
     """Hinge on a voxel signed-distance field, summed over the link points of the FK chain: f(q) = sum_p max(margin - d(p), 0),
@@ -137,3 +141,55 @@ class VoxelDistanceField(DeviceSdf, DistanceField):
     def compute_collision(self, q, chain, buffer=0., **kwargs):
         """Does any link point come closer than `buffer` to an occupied cell? -> bool [..]"""
         return self.compute_distance(q, chain) < buffer
+
+
+class BodyDistanceField(VoxelDistanceField):
+    """The voxel field at a BODY: collision spheres fixed in the link frames, each with its radius (robots/body.py: BodySpheres),
+    f(q) = sum_m max(margin - (d(p_m) - r_m), 0) with p_m = P_l + R_l c_m (include/sgpmp.h: SGPMP_COST_BODY_SDF) -- link
+    geometry with thickness, where VoxelDistanceField sees link origins.  The volume, its rebuild, `update()` and
+    `compute_collision` are VoxelDistanceField's; the point set is the body's (no interpolated points).  Accepted by
+    CostCollision(field=...) in StochGPMP and GPMP (with and without continuous-time factors); not evaluated by the
+    dense-trajectory cost (`dense_cost=` of StochGPMP raises ValueError)."""
+
+    def __init__(self, voxel_map, body, margin, threshold=0., **kwargs):
+        if not len(body):
+            raise ValueError("BodyDistanceField: the body has no spheres")
+        self.body = body
+        super().__init__(voxel_map, margin, threshold=threshold, num_interpolate=0, **kwargs)
+
+    def descriptor(self, sigma, distance=False):
+        return dict(super().descriptor(sigma, distance=distance), kind=L.COST_BODY_SDF, body=self.body)
+
+    def compute_cost(self, link_tensor, **kwargs):
+        """Link frames [.., L, 4, 4] -> the field [..] (`body_eval_kernel`).  The frames carry the rotations and sgpmp_field_eval
+        checks the body's last link against L; the context needs a chain only because sgpmp_set_body checks the link indices
+        against one: a placeholder with as many frames as the body reaches."""
+        shape = link_tensor.shape[:-3]
+        frames = link_tensor.contiguous()
+        key = ("frames", frames.dtype, str(frames.device))
+        if key not in self._engines:
+            eng = Engine(1, 2, 0, 1, tensor_args={"device": frames.device, "dtype": frames.dtype})
+            eng.set_fk([("placeholder", "revolute" if j == 0 else "fixed", (0., 0., 0.), (0., 0., 0.))
+                        for j in range(max(self.body.links[-1], 1))], codegen=False)
+            eng.set_costs([self.descriptor(1.0)])
+            self._engines[key] = eng
+        return self._engines[key].field_eval(0, frames).reshape(shape)
+
+    def _query(self, q, chain, distance=True):
+        n = sum(1 for j in chain if j[1] == "revolute")
+        key = ("distance" if distance else "grad", q.dtype, str(q.device), id(chain))
+        if key not in self._engines:
+            eng = Engine(n, 2, 0, 1, tensor_args={"device": q.device, "dtype": q.dtype})
+            eng.set_fk(chain, codegen=False)
+            eng.set_costs([self.descriptor(1.0, distance=distance)])
+            self._engines[key] = eng
+        return self._engines[key].field_grad(0, q.reshape(-1, n).contiguous())
+
+    def compute_cost_and_grad(self, q, chain, **observations):
+        """Field value [B] and gradient [B, n] at joint configurations q [B, n] (`body_grad_kernel`)."""
+        return self._query(q, chain, distance=False)
+
+    def compute_distance(self, q, chain, **kwargs):
+        """Joint configurations q [.., n] -> the body's minimum clearance min_m (d(p_m) - r_m) [..] (negative in collision): the
+        query flag of the term (`_query` also returns its gradient, through the first arg-min sphere)."""
+        return self._query(q, chain)[0].reshape(q.shape[:-1])
