@@ -65,8 +65,10 @@ enum {
                                    counterpart; defined at sgpmp_grid_sdf_build below)                   */
     SGPMP_COST_VOXEL_SDF = 8,   /* CostCollision + VoxelDistanceField: hinge on a voxel signed-distance field at the link
                                    points (no reference counterpart; defined at sgpmp_voxel_sdf_build below) */
-    SGPMP_COST_BODY_SDF = 9     /* CostCollision + BodyDistanceField: the same hinge at the body's collision spheres, each with
+    SGPMP_COST_BODY_SDF = 9,    /* CostCollision + BodyDistanceField: the same hinge at the body's collision spheres, each with
                                    its radius (no reference counterpart; defined at sgpmp_set_body below) */
+    SGPMP_COST_BODY_SELF = 10   /* CostCollision + BodySelfDistanceField: hinge on the clearance between the body's own spheres,
+                                   over the counted pairs (no reference counterpart; defined at sgpmp_set_body_pairs below) */
 };
 enum { SGPMP_FIELD_RBF = 0, SGPMP_FIELD_SDF = 1, SGPMP_FIELD_OCCUPANCY = 2 };
 #define SGPMP_FLAG_GP_START 1      /* GP term includes the start-state unary factor (CostGP)  */
@@ -77,7 +79,9 @@ enum { SGPMP_FIELD_RBF = 0, SGPMP_FIELD_SDF = 1, SGPMP_FIELD_OCCUPANCY = 2 };
                                       allowed only in a cost list whose single term is this one (else SGPMP_EINVAL), and the
                                       GPMP linearisation refuses a term that carries it.  VOXEL_SDF: the same query, min over
                                       the link points of d and the gradient through the first arg-min point.  BODY_SDF: min over
-                                      the body's spheres of the clearance d - r and the gradient through the first arg-min sphere */
+                                      the body's spheres of the clearance d - r and the gradient through the first arg-min sphere.
+                                      BODY_SELF: min over the counted pairs of the clearance D - r_i - r_j and the gradient through
+                                      the first arg-min pair */
 
 #define SGPMP_MAX_TERMS 8
 #define SGPMP_MAX_JOINTS 16
@@ -586,6 +590,43 @@ int sgpmp_voxel_sdf_build(sgpmp_ctx* ctx, const void* occ, int nz, int ny, int n
  * sgpmp_validate refuse a cost list that holds the term (SGPMP_EINVAL): their kernels do not evaluate it.  SGPMP_ESTATE from
  * sgpmp_set_costs in a build without the kernels (csrc/body_sdf.hip). */
 int sgpmp_set_body(sgpmp_ctx* ctx, const int32_t* links, const double* spheres, int n);
+
+/* ---- body self-collision: sphere pairs with radii and an allowed-pair mask (SGPMP_COST_BODY_SELF) --
+ * The other half of the body above: the body's spheres against each other.  The term uses the context's body of sgpmp_set_body,
+ * p_m(q) = P_l + R_l c_m with radius r_m, and a set of COUNTED pairs -- which spheres can touch is the caller's knowledge (an
+ * ignore list, as in GPMP2, CHOMP and cuRobo).  No reference counterpart (SGPMP_COST_SELF is a Gaussian of the distances between
+ * link origins over all link pairs).
+ *
+ * sgpmp_set_body_pairs: rows HOST uint64[n]; bit j of rows[i] set means pair (i, j) is counted; only bits j > i are read.  n must
+ * equal the body's sphere count; n = 0 clears the pairs.  SGPMP_EINVAL: n not equal to the body's count, a null table with n > 0,
+ * a bit j >= n, a counted pair with both spheres on one link (a constant, almost certainly a mistake), no counted pair at all;
+ * SGPMP_ESTATE: no body.  sgpmp_set_body and sgpmp_set_fk clear the pairs.  Synchronous: the rows are uploaded once to a device
+ * table beside the body's, which the kernels read through the constant address space, wave-uniform.
+ *
+ * The term: sgpmp_cost_desc with sigma -> K = 1 / sigma^2, sigma2 = margin >= 0, data null; num_interpolate must be 0
+ * (SGPMP_EINVAL).  For a counted pair (i, j), i < j in table order:
+ *   D_ij = |p_i - p_j|
+ *   s_ij = D_ij - r_i - r_j                         clearance
+ *   h_ij = (margin + r_i + r_j) - D_ij  where that is > 0, else 0
+ *   f(q) = sum of h_ij over the counted pairs, i ascending, then j ascending;
+ *   the term in a cost list is K * sum over t = 1 .. T-1 of f(q_t).
+ * Gradient: dh_ij/dp_i = -(p_i - p_j) / D_ij where h_ij > 0, and dh_ij/dp_j is its negative; exactly 0 where h_ij = 0, and exactly 0
+ * where D_ij = 0 (the value there is margin + r_i + r_j: no NaN, no division).  df/dq follows by the body term's recurrence,
+ * z_k . ((p - o_k) x g) for every joint k in front of the sphere's link; for a joint in front of both spheres the two forces cancel
+ * (g is parallel to p_i - p_j), so only the joints between the two links act, and a pair behind fixed joints only has a gradient of
+ * exactly 0.  A non-finite coordinate of any counted sphere centre gives NaN in the value and in EVERY gradient entry.
+ * A program that holds the term without a chain, a body and pairs fails with SGPMP_ESTATE and a message that names
+ * sgpmp_set_body_pairs, whatever the call order.
+ * Consumers: sgpmp_cost_eval / sgpmp_step / sgpmp_optimize (sampler + generic sweep + body_self_cost_kernel + update: the sweep
+ * skips the term, body_self_cost_kernel adds it to the costs behind it -- and behind body_cost_kernel where both terms are present,
+ * in program order -- one wave per trajectory, lane = waypoint, one writer per cost element, no atomics, two calls give the same
+ * bits; no fused launch takes the term), sgpmp_field_eval on explicit frames [B, L, 4, 4] (L must exceed the body's last link
+ * index), sgpmp_field_grad, and one of the four field slots of sgpmp_gpmp_linearize (with and without sgpmp_gpmp_set_dense).  With
+ * SGPMP_FLAG_GRID_DISTANCE sgpmp_field_grad returns min over the counted pairs of s_ij and the gradient through the FIRST arg-min
+ * pair (summation order, strict comparison): a query, allowed only as the cost list's single term (else SGPMP_EINVAL) and refused
+ * by GPMP.  sgpmp_dense_cost, sgpmp_dense_cost_grad and sgpmp_validate refuse a cost list that holds the term (SGPMP_EINVAL):
+ * their kernels do not evaluate it.  SGPMP_ESTATE from sgpmp_set_costs in a build without the kernels (csrc/body_self.hip). */
+int sgpmp_set_body_pairs(sgpmp_ctx* ctx, const uint64_t* rows, int n);
 
 /* trajs [B,T,d] -> out [B,T_f,d], ctx dtype, T = dims.traj_len. */
 int sgpmp_interpolate(sgpmp_ctx* ctx, const void* trajs, int64_t batch, int n_sub, double dt, void* out, void* stream);

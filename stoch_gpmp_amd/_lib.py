@@ -16,6 +16,7 @@ COST_GP, COST_GOAL_PRIOR, COST_GRID, COST_SPHERES, COST_SELF, COST_EE_GOAL = 1, 
 COST_GRID_SDF = 7                    # the hinge on a signed-distance grid (envs/obst_map.py: GridDistanceField)
 COST_VOXEL_SDF = 8                   # the hinge on a voxel signed-distance field (envs/voxel_map.py: VoxelDistanceField)
 COST_BODY_SDF = 9                    # ... at the body's collision spheres (envs/voxel_map.py: BodyDistanceField)
+COST_BODY_SELF = 10                  # hinge on the clearance between the body's own spheres (robots/body.py: BodySelfDistanceField)
 MAX_BODY = 64                        # include/sgpmp.h SGPMP_MAX_BODY
 FIELD_RBF, FIELD_SDF, FIELD_OCCUPANCY = 0, 1, 2
 FLAG_GP_START, FLAG_SDF_CLAMP, FLAG_EE_SQUARE, FLAG_GRID_DISTANCE = 1, 16, 32, 64
@@ -86,6 +87,7 @@ SIGNATURES = {
     "sgpmp_set_costs": (_I, [_P, C.POINTER(CostDesc), _I]),
     "sgpmp_set_fk": (_I, [_P, C.POINTER(Joint), _I]),
     "sgpmp_set_body": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(_D), _I]),
+    "sgpmp_set_body_pairs": (_I, [_P, C.POINTER(C.c_uint64), _I]),
     "sgpmp_set_fk_codegen": (_I, [_P, C.c_char_p]),
     "sgpmp_fk_codegen_compile": (_I, [C.c_char_p, _I, C.POINTER(_I64)]),
     "sgpmp_fk_codegen_info": (_I, [_P, C.POINTER(_I), C.POINTER(_D), C.POINTER(_I), C.POINTER(_I)]),

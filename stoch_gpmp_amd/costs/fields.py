@@ -215,3 +215,86 @@ class EESE3DistanceField(DistanceField):
 
     def compute_cost(self, link_tensor, **kwargs):
         return self._field(link_tensor, self.square)
+
+
+class BodySelfDistanceField(DistanceField):
+    """The body against itself: hinge on the clearance between the body's own collision spheres, over the counted pairs,
+    f(q) = sum_(i,j) max((margin + r_i + r_j) - |p_i - p_j|, 0) (include/sgpmp.h: SGPMP_COST_BODY_SELF) -- sphere pairs with
+    radii under an allowed-pair mask, where LinkSelfDistanceField is a Gaussian of the link origins' distances over all link
+    pairs.  `pairs`: the rows of robots/body.py's BodySpheres.pair_rows; None builds them with `min_link_gap` and `ignore`.
+    Accepted by CostCollision(field=...) in StochGPMP and GPMP (with and without continuous-time factors); not evaluated by the
+    dense-trajectory cost (`dense_cost=` of StochGPMP raises ValueError).  The field holds no device data; `update()` changes
+    the margin or the pairs."""
+    works_on_frames = True           # compute_cost takes link frames [.., L, 4, 4]
+
+    def __init__(self, body, margin, pairs=None, min_link_gap=2, ignore=(), **kwargs):
+        super().__init__(**kwargs)
+        if not margin >= 0.:
+            raise ValueError("BodySelfDistanceField: margin must be >= 0")
+        if len(body) < 2:
+            raise ValueError("BodySelfDistanceField: the body needs at least two spheres")
+        self.body = body
+        self.margin = float(margin)
+        self.pairs = tuple(int(r) for r in (body.pair_rows(min_link_gap, ignore) if pairs is None else pairs))
+        if len(self.pairs) != len(body):
+            raise ValueError("BodySelfDistanceField: one pair row per sphere")
+        self.num_pairs = sum(bin(r >> (i + 1)).count("1") for i, r in enumerate(self.pairs))
+
+    def update(self, margin=None, pairs=None):
+        """Change the margin and / or the pair rows; planners and composites that hold the field re-compile their cost program
+        before their next evaluation (the edit counter moves, as for the other fields' `update()`).  -> the field."""
+        if margin is not None:
+            if not margin >= 0.:
+                raise ValueError("BodySelfDistanceField: margin must be >= 0")
+            self.margin = float(margin)
+        if pairs is not None:
+            pairs = tuple(int(r) for r in pairs)
+            if len(pairs) != len(self.body):
+                raise ValueError("BodySelfDistanceField: one pair row per sphere")
+            self.pairs = pairs
+            self.num_pairs = sum(bin(r >> (i + 1)).count("1") for i, r in enumerate(self.pairs))
+        self._engines = {}
+        self._version += 1
+        return self
+
+    def descriptor(self, sigma, distance=False):
+        return dict(kind=L.COST_BODY_SELF, flags=L.FLAG_GRID_DISTANCE if distance else 0, sigma=sigma, sigma2=self.margin,
+                    num_interpolate=0, body=self.body, body_pairs=self.pairs)
+
+    def compute_cost(self, link_tensor, **kwargs):
+        """Link frames [.., L, 4, 4] -> the field [..] (`body_self_eval_kernel`).  The context needs a chain only because
+        sgpmp_set_body checks the link indices against one: a placeholder with as many frames as the body reaches."""
+        shape = link_tensor.shape[:-3]
+        frames = link_tensor.contiguous()
+        key = ("frames", frames.dtype, str(frames.device))
+        if key not in self._engines:
+            eng = Engine(1, 2, 0, 1, tensor_args={"device": frames.device, "dtype": frames.dtype})
+            eng.set_fk([("placeholder", "revolute" if j == 0 else "fixed", (0., 0., 0.), (0., 0., 0.))
+                        for j in range(max(self.body.links[-1], 1))], codegen=False)
+            eng.set_costs([self.descriptor(1.0)])
+            self._engines[key] = eng
+        return self._engines[key].field_eval(0, frames).reshape(shape)
+
+    def _query(self, q, chain, distance=True):
+        n = sum(1 for j in chain if j[1] == "revolute")
+        key = ("distance" if distance else "grad", q.dtype, str(q.device), id(chain))
+        if key not in self._engines:
+            eng = Engine(n, 2, 0, 1, tensor_args={"device": q.device, "dtype": q.dtype})
+            eng.set_fk(chain, codegen=False)
+            eng.set_costs([self.descriptor(1.0, distance=distance)])
+            self._engines[key] = eng
+        return self._engines[key].field_grad(0, q.reshape(-1, n).contiguous())
+
+    def compute_cost_and_grad(self, q, chain, **observations):
+        """Field value [B] and gradient [B, n] at joint configurations q [B, n] (`body_self_grad_kernel`)."""
+        return self._query(q, chain, distance=False)
+
+    def compute_distance(self, q, chain, **kwargs):
+        """Joint configurations q [.., n] -> the minimum clearance over the counted pairs, min (|p_i - p_j| - r_i - r_j) [..]
+        (negative in self-collision): the query flag of the term (`_query` also returns its gradient, through the first
+        arg-min pair)."""
+        return self._query(q, chain)[0].reshape(q.shape[:-1])
+
+    def compute_collision(self, q, chain, buffer=0., **kwargs):
+        """Does any counted pair come closer than `buffer`? -> bool [..]"""
+        return self.compute_distance(q, chain) < buffer

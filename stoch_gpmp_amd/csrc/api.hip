@@ -112,6 +112,9 @@ struct sgpmp_ctx {
     void* d_body = nullptr;
     int n_body = 0;                  // 0: no body
     int body_last_link = 0;          // the largest link index of the table
+    std::vector<int32_t> h_body_links;   // the table's link indices (sgpmp_set_body_pairs checks pairs against them)
+    // the counted pairs of SGPMP_COST_BODY_SELF (sgpmp_set_body_pairs): uint64 rows[SGPMP_MAX_BODY] behind the body's table in d_body
+    int n_body_pairs = 0;            // 0: no pairs
 };
 
 // name -> field of SgpmpToggles (environment variable = "SGPMP_" + upper-case name)
@@ -743,6 +746,22 @@ extern "C" int sgpmp_set_costs(sgpmp_ctx* c, const sgpmp_cost_desc* descs, int n
                 t.dt = s.dt;                                      // the z offset (TermK::dt)
                 t.K2 = s.sigma2;                                  // the hinge's margin (TermK::K2)
                 break;
+            case SGPMP_COST_BODY_SELF:
+                // K and the margin only; the spheres come from sgpmp_set_body and the pairs from sgpmp_set_body_pairs
+                // (finalize_program joins the three).  Not a field of the sweep: body_self_cost_kernel walks the chain itself
+                if (!launch_body_self_cost || !launch_body_self_grad || !launch_body_self_eval)
+                    return fail(SGPMP_ESTATE, "sgpmp_set_costs: this build has no body_self kernels (SGPMP_COST_BODY_SELF)");
+                if (s.data || !(s.sigma2 >= 0.) || !std::isfinite(s.sigma2))
+                    return fail(SGPMP_EINVAL, "sgpmp_set_costs: body self-distance term takes no data and a finite margin >= 0");
+                if (c->dims.n_dof < 1)
+                    return fail(SGPMP_EINVAL, "sgpmp_set_costs: body self-distance term needs n_dof >= 1");
+                if ((s.flags & SGPMP_FLAG_GRID_DISTANCE) && n_desc != 1)
+                    return fail(SGPMP_EINVAL, "sgpmp_set_costs: SGPMP_FLAG_GRID_DISTANCE is a query flag for sgpmp_field_grad: "
+                                              "the term must be the cost list's only one");
+                if (s.num_interpolate != 0)
+                    return fail(SGPMP_EINVAL, "sgpmp_set_costs: body self-distance term takes no interpolated points (num_interpolate must be 0)");
+                t.K2 = s.sigma2;                                  // the hinge's margin (TermK::K2)
+                break;
             case SGPMP_COST_SPHERES:
             case SGPMP_COST_SELF:
                 if (s.num_interpolate < 0 || s.num_interpolate > SGPMP_MAX_INTERP)
@@ -934,6 +953,7 @@ extern "C" int sgpmp_set_fk(sgpmp_ctx* c, const sgpmp_joint* chain, int n_joints
     c->have_chain = true;
     c->prog_dirty = true;
     c->n_body = 0;                                               // the body's link indices belonged to the old chain
+    c->n_body_pairs = 0;
     return SGPMP_OK;
 }
 
@@ -955,6 +975,7 @@ extern "C" int sgpmp_set_body(sgpmp_ctx* c, const int32_t* links, const double* 
         return fail(SGPMP_EINVAL, "sgpmp_set_body: link index past the chain's last frame");
     c->prog_dirty = true;
     c->n_body = 0;
+    c->n_body_pairs = 0;                                         // the pairs were pairs of the old table
     if (n == 0) return SGPMP_OK;
     const size_t link_bytes = SGPMP_MAX_BODY * sizeof(int32_t), bytes = link_bytes + (size_t)SGPMP_MAX_BODY * 4 * c->esz;
     std::vector<unsigned char> host(bytes, 0);
@@ -964,10 +985,40 @@ extern "C" int sgpmp_set_body(sgpmp_ctx* c, const int32_t* links, const double* 
         else reinterpret_cast<float*>(host.data() + link_bytes)[i] = (float)spheres[i];
     }
     HIPCHK(hipDeviceSynchronize());                              // (a launch in flight may still read the old table)
-    if (!c->d_body) HIPCHK(hipMalloc(&c->d_body, bytes));
+    if (!c->d_body) HIPCHK(hipMalloc(&c->d_body, bytes + SGPMP_MAX_BODY * sizeof(uint64_t)));     // (+ the pair rows)
+    c->h_body_links.assign(links, links + n);
     HIPCHK(hipMemcpy(c->d_body, host.data(), bytes, hipMemcpyHostToDevice));
     c->n_body = n;
     c->body_last_link = links[n - 1];
+    return SGPMP_OK;
+}
+
+// The counted pairs of SGPMP_COST_BODY_SELF (include/sgpmp.h): checked on the host, uploaded once behind the body's table.
+extern "C" int sgpmp_set_body_pairs(sgpmp_ctx* c, const uint64_t* rows, int n) {
+    if (!c) return fail(SGPMP_EINVAL, "sgpmp_set_body_pairs: null context");
+    if (c->n_body < 1) return fail(SGPMP_ESTATE, "sgpmp_set_body_pairs: no body (sgpmp_set_body first)");
+    c->prog_dirty = true;
+    if (n == 0) { c->n_body_pairs = 0; return SGPMP_OK; }
+    if (n != c->n_body) return fail(SGPMP_EINVAL, "sgpmp_set_body_pairs: n must equal the body's sphere count (or 0 to clear)");
+    if (!rows) return fail(SGPMP_EINVAL, "sgpmp_set_body_pairs: null table");
+    uint64_t host[SGPMP_MAX_BODY] = {};
+    int pairs = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint64_t upper = i < 63 ? rows[i] & ~((2ULL << i) - 1ULL) : 0ULL;       // only bits j > i are read
+        if (n < 64 && (upper >> n)) return fail(SGPMP_EINVAL, "sgpmp_set_body_pairs: a bit j >= n is set");
+        for (int j = i + 1; j < n; ++j)
+            if (upper >> j & 1ULL) {
+                if (c->h_body_links[i] == c->h_body_links[j])
+                    return fail(SGPMP_EINVAL, "sgpmp_set_body_pairs: a counted pair has both spheres on one link (a constant)");
+                ++pairs;
+            }
+        host[i] = upper;
+    }
+    if (pairs == 0) return fail(SGPMP_EINVAL, "sgpmp_set_body_pairs: no counted pair");
+    const size_t offset = SGPMP_MAX_BODY * sizeof(int32_t) + (size_t)SGPMP_MAX_BODY * 4 * c->esz;
+    HIPCHK(hipDeviceSynchronize());                              // (a launch in flight may still read the old rows)
+    HIPCHK(hipMemcpy((char*)c->d_body + offset, host, sizeof(host), hipMemcpyHostToDevice));
+    c->n_body_pairs = pairs;
     return SGPMP_OK;
 }
 
@@ -1033,6 +1084,14 @@ static int finalize_program(sgpmp_ctx* c) {
                 return fail(SGPMP_ESTATE, "the body distance term (SGPMP_COST_BODY_SDF) needs an FK chain and a body: "
                                           "sgpmp_set_fk, then sgpmp_set_body");
             t.body = c->d_body;
+            t.n_body = c->n_body;
+            continue;
+        }
+        if (t.kind == SGPMP_COST_BODY_SELF) {      // the term, the body and the pairs meet here, in whichever order they were set
+            if (!c->have_chain || c->n_body < 1 || c->n_body_pairs < 1)
+                return fail(SGPMP_ESTATE, "the body self-distance term (SGPMP_COST_BODY_SELF) needs an FK chain, a body and counted "
+                                          "pairs: sgpmp_set_fk, sgpmp_set_body, then sgpmp_set_body_pairs");
+            t.body = c->d_body;                    // (the pair rows lie behind the table: body_self.hip make_bodyselfk)
             t.n_body = c->n_body;
             continue;
         }
@@ -1373,7 +1432,7 @@ static int run_range(sgpmp_ctx* c, const StepPlan& plan, const StepArgs& a, size
                            &c->last_cost_kernel));
         launches += 2;
         for (int i = 0; i < c->h_prog.n_terms; ++i)                 // (body_cost_kernel behind the sweep, once per body term)
-            if (c->h_prog.terms[i].kind == SGPMP_COST_BODY_SDF) launches += 1;
+            if (c->h_prog.terms[i].kind == SGPMP_COST_BODY_SDF || c->h_prog.terms[i].kind == SGPMP_COST_BODY_SELF) launches += 1;
     }
     HT(2);                                                       // the fused launch (or sampler + sweep)
     if (se) HIPCHK(hipEventRecord(se->ev[3], st));
@@ -1637,6 +1696,14 @@ extern "C" int sgpmp_field_eval(sgpmp_ctx* c, int term, const void* frames, int6
         HIPCHK(launch_body_eval(c->dims.dtype, c->h_prog.terms[term], frames, batch, n_links, out, (hipStream_t)stream));
         return SGPMP_OK;
     }
+    if (c->h_prog.terms[term].kind == SGPMP_COST_BODY_SELF) {    // the counted pairs of the body's spheres in the given frames
+        int rc;
+        if ((rc = finalize_program(c)) != SGPMP_OK) return rc;
+        if (n_links <= c->body_last_link)
+            return fail(SGPMP_EINVAL, "sgpmp_field_eval: the body has a sphere on a link past the given frames");
+        HIPCHK(launch_body_self_eval(c->dims.dtype, c->h_prog.terms[term], frames, batch, n_links, out, (hipStream_t)stream));
+        return SGPMP_OK;
+    }
     CostTerm t = c->h_prog.terms[term];
     if (t.kind != SGPMP_COST_SPHERES && t.kind != SGPMP_COST_SELF && t.kind != SGPMP_COST_EE_GOAL &&
         t.kind != SGPMP_COST_VOXEL_SDF)
@@ -1676,6 +1743,8 @@ static int term_value_grad(sgpmp_ctx* c, const CostTerm& t, const void* q, long 
         HIPCHK(launch_grid_sdf_grad(dtype, n, t, q, batch, traj_T, value, grad, st));
     } else if (t.kind == SGPMP_COST_BODY_SDF) {           // the body's spheres: a walk of its own (body_sdf.hip)
         HIPCHK(launch_body_grad(dtype, n, t, c->d_chain, c->h_chain.n_joints, q, batch, traj_T, value, grad, st));
+    } else if (t.kind == SGPMP_COST_BODY_SELF) {          // the body's sphere pairs (body_self.hip)
+        HIPCHK(launch_body_self_grad(dtype, n, t, c->d_chain, c->h_chain.n_joints, q, batch, traj_T, value, grad, st));
     } else if (t.kind != SGPMP_COST_EE_GOAL) {
         HIPCHK(launch_field_grad(dtype, n, t, c->d_chain, c->h_chain.n_joints, q, batch, traj_T, spheres, n_spheres, value,
                                  grad, st));
@@ -1703,6 +1772,9 @@ extern "C" int sgpmp_field_grad(sgpmp_ctx* c, int term, const void* q, int64_t b
             return fail(SGPMP_ESTATE, "sgpmp_field_grad: the voxel distance term needs an FK chain (sgpmp_set_fk)");
         if (c->h_prog.terms[term].kind == SGPMP_COST_BODY_SDF && !c->have_chain)
             return fail(SGPMP_ESTATE, "sgpmp_field_grad: the body distance term needs an FK chain and a body (sgpmp_set_fk, sgpmp_set_body)");
+        if (c->h_prog.terms[term].kind == SGPMP_COST_BODY_SELF && !c->have_chain)
+            return fail(SGPMP_ESTATE, "sgpmp_field_grad: the body self-distance term needs an FK chain, a body and counted pairs "
+                                      "(sgpmp_set_fk, sgpmp_set_body, sgpmp_set_body_pairs)");
         if (!c->have_chain) return fail(SGPMP_EINVAL, "sgpmp_field_grad: no FK chain (sgpmp_set_fk)");
         int rc;
         if ((rc = finalize_program(c)) != SGPMP_OK) return rc;
@@ -1712,7 +1784,7 @@ extern "C" int sgpmp_field_grad(sgpmp_ctx* c, int term, const void* q, int64_t b
                 return fail(SGPMP_EINVAL, "sgpmp_field_grad: the occupancy count has no gradient (rbf and sdf sphere fields do)");
             if (!spheres || n_spheres < 1) return fail(SGPMP_EINVAL, "LinkDistanceField cost needs obstacle_spheres");
         } else if (t.kind != SGPMP_COST_EE_GOAL && t.kind != SGPMP_COST_SELF && t.kind != SGPMP_COST_VOXEL_SDF &&
-                   t.kind != SGPMP_COST_BODY_SDF) {
+                   t.kind != SGPMP_COST_BODY_SDF && t.kind != SGPMP_COST_BODY_SELF) {
             return fail(SGPMP_EINVAL, "sgpmp_field_grad: term is not a smooth link field");
         }
         if (t.kind != SGPMP_COST_EE_GOAL && t.n_points > SGPMP_MAX_POINTS)
@@ -1750,7 +1822,10 @@ static int gpmp_args(sgpmp_ctx* c, GpmpArgs& a, int* field_terms) {
             case SGPMP_COST_SELF:
             case SGPMP_COST_VOXEL_SDF:                    // (a link field like SPHERES: launch_field_grad)
             case SGPMP_COST_BODY_SDF:                     // (the body's spheres: launch_body_grad)
+            case SGPMP_COST_BODY_SELF:                    // (the body's sphere pairs: launch_body_self_grad)
             case SGPMP_COST_GRID_SDF:                     // (a field of the planar point: no FK chain)
+                if (t.kind == SGPMP_COST_BODY_SELF && (t.flags & SGPMP_FLAG_GRID_DISTANCE))
+                    return fail(SGPMP_EINVAL, "GPMP: a body self-distance term with SGPMP_FLAG_GRID_DISTANCE is a query, not a cost");
                 if ((t.kind == SGPMP_COST_GRID_SDF || t.kind == SGPMP_COST_VOXEL_SDF || t.kind == SGPMP_COST_BODY_SDF) &&
                     (t.flags & SGPMP_FLAG_GRID_DISTANCE))
                     return fail(SGPMP_EINVAL, t.kind == SGPMP_COST_GRID_SDF

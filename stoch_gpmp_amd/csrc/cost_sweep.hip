@@ -388,6 +388,21 @@ static const char* body_sweep_name(const char* sweep) {
     return "cost sweep + body_cost_kernel";
 }
 
+// The same for body_self_cost_kernel, behind a bare sweep or behind body_cost_kernel (program order: the body term first).
+static const char* body_self_sweep_name(const char* sweep) {
+#define BSELF_NAMES(s) {s, s " + body_self_cost_kernel"}, {s " + body_cost_kernel", s " + body_cost_kernel + body_self_cost_kernel"}
+    static const char* const names[][2] = {
+        BSELF_NAMES("cost_sweep_kernel<f32, generated chain>"), BSELF_NAMES("cost_sweep_kernel<f64, generated chain>"),
+        BSELF_NAMES("cost_sweep_kernel<f32, register FK>"), BSELF_NAMES("cost_sweep_kernel<f64, register FK>"),
+        BSELF_NAMES("cost_sweep_kernel<f32, generic FK>"), BSELF_NAMES("cost_sweep_kernel<f64, generic FK>"),
+        BSELF_NAMES("cost_sweep_kernel<f32, no FK>"), BSELF_NAMES("cost_sweep_kernel<f64, no FK>"),
+    };
+#undef BSELF_NAMES
+    for (const auto& n : names)
+        if (std::strcmp(sweep, n[0]) == 0 || std::strcmp(sweep, n[1]) == 0) return n[1];
+    return "cost sweep + body_self_cost_kernel";
+}
+
 hipError_t launch_cost(int dtype, int n, int T, const CostProgram& h_prog, const ChainDev* d_chain,
                        const ChainDev& h_chain, const void* trajs, long long batch,
                        long long batch_offset, const void* spheres, int n_spheres,
@@ -410,11 +425,16 @@ hipError_t launch_cost(int dtype, int n, int T, const CostProgram& h_prog, const
             e = launch_ee_goal(dtype, n, T, h_prog.terms[i], d_chain, trajs, batch, costs, costs64, stream);
     // body collision spheres (SGPMP_COST_BODY_SDF): the sweep skips the kind; body_cost_kernel (body_sdf.hip) adds the term to
     // the costs in the same way, one wave per trajectory
+    // the body's sphere pairs (SGPMP_COST_BODY_SELF): likewise body_self_cost_kernel (body_self.hip); the two kinds in program order
     for (int i = 0; i < h_prog.n_terms && e == hipSuccess; ++i)
         if (h_prog.terms[i].kind == SGPMP_COST_BODY_SDF) {
             if (!launch_body_cost) return hipErrorInvalidValue;      // (a build without body_sdf.hip: sgpmp_set_costs has refused)
             e = launch_body_cost(dtype, n, T, h_prog.terms[i], d_chain, trajs, batch, costs, costs64, stream);
             if (e == hipSuccess && picked) *picked = body_sweep_name(*picked);
+        } else if (h_prog.terms[i].kind == SGPMP_COST_BODY_SELF) {
+            if (!launch_body_self_cost) return hipErrorInvalidValue; // (a build without body_self.hip: likewise)
+            e = launch_body_self_cost(dtype, n, T, h_prog.terms[i], d_chain, trajs, batch, costs, costs64, stream);
+            if (e == hipSuccess && picked) *picked = body_self_sweep_name(*picked);
         }
     return e;
 }

@@ -462,6 +462,14 @@ hipError_t launch_body_grad(int dtype, int n, const CostTerm& term, const ChainD
                             long long batch, int traj_T, void* value, void* grad, hipStream_t stream) __attribute__((weak));
 hipError_t launch_body_eval(int dtype, const CostTerm& term, const void* frames, long long batch, int n_links, void* out,
                             hipStream_t stream) __attribute__((weak));
+// SGPMP_COST_BODY_SELF (body_self.hip; term.body / term.n_body: the table, with the pair rows of sgpmp_set_body_pairs behind it;
+// term.K2: the margin): the same three launches for the body's sphere pairs, with the same arguments.  Weak for the same reason.
+hipError_t launch_body_self_cost(int dtype, int n, int T, const CostTerm& term, const ChainDev* d_chain, const void* trajs,
+                                 long long batch, void* costs, double* costs64, hipStream_t stream) __attribute__((weak));
+hipError_t launch_body_self_grad(int dtype, int n, const CostTerm& term, const ChainDev* d_chain, int n_joints, const void* q,
+                                 long long batch, int traj_T, void* value, void* grad, hipStream_t stream) __attribute__((weak));
+hipError_t launch_body_self_eval(int dtype, const CostTerm& term, const void* frames, long long batch, int n_links, void* out,
+                                 hipStream_t stream) __attribute__((weak));
 hipError_t launch_link_dist(int dtype, const void* frames, long long batch, int n_links, const void* spheres,
                             int n_other, int mode, double buffer, void* out, hipStream_t stream);
 hipError_t launch_fk(int dtype, int n, const ChainDev* d_chain, int n_links, const void* q,

@@ -408,7 +408,7 @@ extern "C" int sgpmp_interpolate(sgpmp_ctx* c, const void* trajs, int64_t batch,
     return e == hipSuccess ? SGPMP_OK : dense_hip_error("sgpmp_interpolate", e);
 }
 
-// The dense-trajectory kernels do not evaluate SGPMP_COST_VOXEL_SDF or SGPMP_COST_BODY_SDF: a cost list that holds the term is refused by name, never
+// The dense-trajectory kernels do not evaluate SGPMP_COST_VOXEL_SDF, SGPMP_COST_BODY_SDF or SGPMP_COST_BODY_SELF: a cost list that holds the term is refused by name, never
 // evaluated without it (which would drop a collision term).  -> the message, or null.
 static const char* voxel_term_refusal(const char* who, const SgpmpCtxView& v) {
     static thread_local char msg[200];
@@ -420,6 +420,10 @@ static const char* voxel_term_refusal(const char* who, const SgpmpCtxView& v) {
         } else if (v.prog->terms[i].kind == SGPMP_COST_BODY_SDF) {          // (the same holds for the body's spheres on that field)
             snprintf(msg, sizeof(msg), "%s: cost term %d (SGPMP_COST_BODY_SDF) is not evaluated on dense trajectories; "
                                        "the body distance term counts at the support waypoints only", who, i);
+            return msg;
+        } else if (v.prog->terms[i].kind == SGPMP_COST_BODY_SELF) {         // (and for the body's sphere pairs)
+            snprintf(msg, sizeof(msg), "%s: cost term %d (SGPMP_COST_BODY_SELF) is not evaluated on dense trajectories; "
+                                       "the body self-distance term counts at the support waypoints only", who, i);
             return msg;
         }
     return nullptr;

@@ -47,7 +47,8 @@ class Engine:
             L.check(self.lib.sgpmp_create(C.byref(self.dims), C.byref(self._ctx)))
         self._keep = []          # tensors whose device memory the cost program points at
         self.n_links = None
-        self._prior_key = {}     # which -> arguments of the last successful set_prior
+        self.body = self.body_pairs = None   # what set_body / set_body_pairs last handed to the context
+        self._prior_key = {}    # which -> arguments of the last successful set_prior
         self._prior_modes = {}   # which -> number of per-mode factors after set_prior_blocks (absent: one shared factor)
 
     def close(self):
@@ -293,8 +294,13 @@ class Engine:
         bodies = [dsc["body"] for dsc in descs if dsc.get("body") is not None]
         if any(b != bodies[0] for b in bodies[1:]):
             raise ValueError("Engine.set_costs: two different bodies in one cost list (a context holds one body)")
+        pairs = [tuple(dsc["body_pairs"]) for dsc in descs if dsc.get("body_pairs") is not None]
+        if any(p != pairs[0] for p in pairs[1:]):
+            raise ValueError("Engine.set_costs: two different pair tables in one cost list (a context holds one)")
         if bodies:                                      # (before the program: sgpmp_set_costs itself does not need it yet)
             self.set_body(bodies[0])
+        if pairs:                                       # (after the body, which clears them)
+            self.set_body_pairs(pairs[0])
         arr = (L.CostDesc * max(len(descs), 1))()
         self._keep = []
         host_keep = []
@@ -337,6 +343,7 @@ class Engine:
         with torch.cuda.device(self.device):
             L.check(self.lib.sgpmp_set_fk(self._ctx, arr, len(chain)))
         self.n_links = len(chain) + 1
+        self.body = self.body_pairs = None              # (sgpmp_set_fk clears the body and its pairs)
         self.fk_codegen_error = None
         if codegen and self.fk_codegen_info()[0] == 0 and self.dtype == torch.float32 and self.n <= 7 \
                 and not os.environ.get("SGPMP_NO_RTC"):
@@ -359,6 +366,18 @@ class Engine:
         with torch.cuda.device(self.device):
             L.check(self.lib.sgpmp_set_body(self._ctx, links, sph, n))
         self.body = body if n else None
+        self.body_pairs = None                          # (sgpmp_set_body clears the pairs)
+
+    def set_body_pairs(self, rows):
+        """The counted pairs of SGPMP_COST_BODY_SELF (BodySpheres.pair_rows: one uint64 per sphere, bit j of rows[i] = pair (i, j);
+        None or empty to clear): sgpmp_set_body_pairs.  Needs the body (set_body first); a later set_body or set_fk clears them."""
+        rows = [] if rows is None else [int(v) for v in rows]
+        if any(not 0 <= v < 2 ** 64 for v in rows):
+            raise ValueError("Engine.set_body_pairs: a row is a uint64")
+        arr = (C.c_uint64 * max(len(rows), 1))(*(rows or [0]))
+        with torch.cuda.device(self.device):
+            L.check(self.lib.sgpmp_set_body_pairs(self._ctx, arr, len(rows)))
+        self.body_pairs = tuple(rows) if rows else None
 
     def fk_codegen_info(self):
         """(codegen_id, seconds in hiprtc, code objects compiled, taken from the disk cache); codegen_id: 0 run-time

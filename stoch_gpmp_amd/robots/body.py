@@ -41,6 +41,14 @@ class BodySpheres:
         """-> [M][4] rows (cx, cy, cz, r), the layout of sgpmp_set_body."""
         return [list(c) + [r] for c, r in zip(self.centers, self.radii)]
 
+    def pair_rows(self, min_link_gap=2, ignore=()):
+        """-> the rows of sgpmp_set_body_pairs, one int (uint64) per sphere: bit j of rows[i], j > i, is set where the spheres'
+        link indices differ by at least `min_link_gap` and the link pair is not in `ignore` (pairs of link indices, in either
+        order).  Neighbouring links touch at their joint by construction, hence the default gap of 2.  ValueError when nothing
+        is counted (or when min_link_gap < 1: a pair on one link is a constant)."""
+        from ..body_self import pair_rows                                   # (the numpy twin holds the rule)
+        return pair_rows(self.links, min_link_gap, ignore)
+
     @classmethod
     def along_links(cls, chain, spacing, radius):
         """Spheres of one radius strung along the chain, from its constants alone: joint l (0-based), whose offset `xyz` is
