@@ -751,6 +751,9 @@ int sgpmp_gpmp_set_dense(sgpmp_ctx* ctx, int n_sub, double dt, double weight, co
 /* Name of the solve kernel of this thread's last sgpmp_gpmp_solve ("gpmp_thomas_kernel", "gpmp_solve_kernel",
  * "gpmp_dense_solve_kernel"; "" before): for the tests that must prove which kernel they exercised.  Static string. */
 const char* sgpmp_last_gpmp_kernel(void);
+/* Particles per wave of that solve: 4 or 2 after "gpmp_thomas_kernel" (four while 4 x 8 T (32 + 9 F) bytes of staging, F the number
+ * of link-field terms, fit 150 KiB of LDS; else two), 0 after the other two kernels and before the first solve. */
+int sgpmp_last_gpmp_ppw(void);
 
 /* Kernel timing helper for bench.py: elapsed ms between two events recorded on `stream`
  * (HIP events on the stream the kernels run on). */

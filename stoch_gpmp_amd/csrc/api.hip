@@ -1833,7 +1833,7 @@ static int gpmp_args(sgpmp_ctx* c, GpmpArgs& a, int* field_terms) {
                         : t.kind == SGPMP_COST_VOXEL_SDF
                         ? "GPMP: a voxel distance term with SGPMP_FLAG_GRID_DISTANCE is a query, not a cost"
                         : "GPMP: a body distance term with SGPMP_FLAG_GRID_DISTANCE is a query, not a cost");
-                if (a.n_fields == 4) return fail(SGPMP_EINVAL, "GPMP: more than 4 link-field terms");
+                if (a.n_fields == SGPMP_MAX_GPMP_FIELDS) return fail(SGPMP_EINVAL, "GPMP: more than 4 link-field terms");
                 field_terms[a.n_fields] = i;
                 a.f[a.n_fields].K = t.K;
                 a.n_fields += 1;
@@ -1897,7 +1897,9 @@ extern "C" int sgpmp_gpmp_set_dense(sgpmp_ctx* c, int n_sub, double dt, double w
 }
 
 static thread_local const char* g_last_gpmp_kernel = "";
+static thread_local int g_last_gpmp_ppw = 0;          // particles per wave of that solve (gpmp_thomas_kernel), else 0
 extern "C" const char* sgpmp_last_gpmp_kernel(void) { return g_last_gpmp_kernel; }
+extern "C" int sgpmp_last_gpmp_ppw(void) { return g_last_gpmp_ppw; }
 
 extern "C" int sgpmp_gpmp_linearize(sgpmp_ctx* c, const void* means, const void* spheres, int n_spheres,
                                     double* diag_sum, void* stream) {
@@ -1965,6 +1967,7 @@ extern "C" int sgpmp_gpmp_solve(sgpmp_ctx* c, void* means, const double* diag_su
             c->gdense.k.inserted[k] = c->h_prog.terms[ft[k]].kind == SGPMP_COST_EE_GOAL ? 0 : 1;
         HIPCHK(launch_gpmp_dense_solve(c->dims.dtype, a, c->gdense.k, means, d_theta, costs, st));
         g_last_gpmp_kernel = "gpmp_dense_solve_kernel";
+        g_last_gpmp_ppw = 0;
     } else {
         if (c->g_fine1 != (size_t)a.T - 1)
             return fail(SGPMP_ESTATE, "sgpmp_gpmp_solve: call sgpmp_gpmp_linearize after sgpmp_gpmp_set_dense");
@@ -1972,6 +1975,7 @@ extern "C" int sgpmp_gpmp_solve(sgpmp_ctx* c, void* means, const double* diag_su
         const bool thomas = !c->tg.gpmp_cholesky && (a.n == 2 || a.n == 3 || a.n == 6 || a.n == 7);
         HIPCHK(launch_gpmp_solve(c->dims.dtype, a, means, d_theta, costs, st, c->tg.gpmp_cholesky != 0));
         g_last_gpmp_kernel = thomas ? "gpmp_thomas_kernel" : "gpmp_solve_kernel";
+        g_last_gpmp_ppw = thomas ? gpmp_solve_layout(a.T, a.n_fields).ppw : 0;
     }
     int status = 0;                                   // synchronous, like sgpmp_set_prior: GPMP is not the hot path
     HIPCHK(hipMemcpyAsync(&status, c->d_gstatus, sizeof(int), hipMemcpyDeviceToHost, st));

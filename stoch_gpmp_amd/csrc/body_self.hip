@@ -28,13 +28,6 @@ static size_t body_self_lds(int dtype, int n_body) {
     return (size_t)3 * n_body * SGPMP_WAVE * (dtype == SGPMP_F64 ? sizeof(double) : sizeof(float));
 }
 
-// A request above 64 KiB needs the kernel's dynamic-LDS limit raised first (a gfx950 workgroup may use up to 160 KiB).
-template <typename Kernel>
-static hipError_t body_self_allow_lds(Kernel kernel, size_t bytes) {
-    if (bytes <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 template <typename real>
 __device__ __forceinline__ real* body_self_image() {
     extern __shared__ __attribute__((aligned(16))) unsigned char body_self_smem[];
@@ -73,11 +66,11 @@ hipError_t launch_body_self_cost(int dtype, int n, int T, const CostTerm& term, 
     const size_t lds = body_self_lds(dtype, term.n_body);
     hipError_t e;
     if (dtype == SGPMP_F64) {
-        if ((e = body_self_allow_lds(body_self_cost_kernel<double>, lds)) != hipSuccess) return e;
+        if ((e = sgpmp_allow_lds(body_self_cost_kernel<double>, lds)) != hipSuccess) return e;
         hipLaunchKernelGGL((body_self_cost_kernel<double>), dim3((unsigned)batch), dim3(SGPMP_WAVE), lds, stream, d_chain, term.K,
                            term.K2, make_bodyselfk<double>(term), n, T, (const double*)trajs, batch, (double*)costs, costs64);
     } else {
-        if ((e = body_self_allow_lds(body_self_cost_kernel<float>, lds)) != hipSuccess) return e;
+        if ((e = sgpmp_allow_lds(body_self_cost_kernel<float>, lds)) != hipSuccess) return e;
         hipLaunchKernelGGL((body_self_cost_kernel<float>), dim3((unsigned)batch), dim3(SGPMP_WAVE), lds, stream, d_chain,
                            (float)term.K, (float)term.K2, make_bodyselfk<float>(term), n, T, (const float*)trajs, batch,
                            (float*)costs, costs64);
@@ -121,7 +114,7 @@ hipError_t launch_body_self_grad(int dtype, int n, const CostTerm& term, const C
     hipError_t e = hipSuccess;
 #define BSG_LAUNCH(REAL, NJ, MODE)                                                                  \
     do {                                                                                            \
-        if ((e = body_self_allow_lds(body_self_grad_kernel<REAL, NJ, MODE>, lds)) != hipSuccess) return e; \
+        if ((e = sgpmp_allow_lds(body_self_grad_kernel<REAL, NJ, MODE>, lds)) != hipSuccess) return e; \
         hipLaunchKernelGGL((body_self_grad_kernel<REAL, NJ, MODE>), dim3(grid), dim3(block), lds, stream, d_chain, \
                            (REAL)term.K2, make_bodyselfk<REAL>(term), n, (const REAL*)q, batch, traj_T, \
                            (REAL*)value, (REAL*)grad);                                              \
@@ -161,11 +154,11 @@ hipError_t launch_body_self_eval(int dtype, const CostTerm& term, const void* fr
     const size_t lds = body_self_lds(dtype, term.n_body);
     hipError_t e;
     if (dtype == SGPMP_F64) {
-        if ((e = body_self_allow_lds(body_self_eval_kernel<double>, lds)) != hipSuccess) return e;
+        if ((e = sgpmp_allow_lds(body_self_eval_kernel<double>, lds)) != hipSuccess) return e;
         hipLaunchKernelGGL((body_self_eval_kernel<double>), dim3(grid), dim3(block), lds, stream, (double)term.K2,
                            make_bodyselfk<double>(term), (const double*)frames, batch, n_links, (double*)out);
     } else {
-        if ((e = body_self_allow_lds(body_self_eval_kernel<float>, lds)) != hipSuccess) return e;
+        if ((e = sgpmp_allow_lds(body_self_eval_kernel<float>, lds)) != hipSuccess) return e;
         hipLaunchKernelGGL((body_self_eval_kernel<float>), dim3(grid), dim3(block), lds, stream, (float)term.K2,
                            make_bodyselfk<float>(term), (const float*)frames, batch, n_links, (float*)out);
     }

@@ -295,19 +295,16 @@ gpmp_solve_kernel(GpmpArgs a, real* __restrict__ means, real* __restrict__ d_the
 //     v_readlane with literal lane numbers: no LDS, no barrier inside the elimination (round 3's column-by-column Cholesky
 //     through LDS paid two barriers and an fp64 sqrt + division per column, 14 us per waypoint; this is ~1.5 us);
 //   * M_t rows are parked for the backward sweep (d x d doubles per waypoint instead of two 16 x 16 tiles).
-// PPW particles per wave, one per row of 16 lanes (a single wave is ISSUE-bound on this recursion -- ~2500 instructions per
+// PPW particles per wave (4 or 2: gpmp_solve_layout, sgpmp_internal.h), one per row of 16 lanes (a single wave is ISSUE-bound on this recursion -- ~2500 instructions per
 // waypoint at one per 4 cycles -- and a lane-row layout leaves 50 of 64 lanes idle: four particles share every instruction).
 // The pivot-row broadcast is then per 16-lane row: DPP row_newbcast instead of v_readlane.
 template <int PPW, int K>
 __device__ __forceinline__ double row_bcast(double v) {
-    if constexpr (PPW == 1) {
-        return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), K), __builtin_amdgcn_readlane(__double2loint(v), K));
-    } else {
-        // (every lane of a row has a source lane: the `old` operand is never kept -- handing the source itself spares a move)
-        const int hi = __double2hiint(v), lo = __double2loint(v);
-        return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0x150 + K, 0xf, 0xf, true),
-                                __builtin_amdgcn_update_dpp(lo, lo, 0x150 + K, 0xf, 0xf, true));
-    }
+    static_assert(PPW == 2 || PPW == 4, "one particle per row of 16 lanes");
+    // (every lane of a row has a source lane: the `old` operand is never kept -- handing the source itself spares a move)
+    const int hi = __double2hiint(v), lo = __double2loint(v);
+    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0x150 + K, 0xf, 0xf, true),
+                            __builtin_amdgcn_update_dpp(lo, lo, 0x150 + K, 0xf, 0xf, true));
 }
 // dst[c] = lane c's value of v, for every c (lane numbers must be literals: recursion over the index)
 template <int PPW, int D, int C = 0>
@@ -337,10 +334,14 @@ gpmp_thomas_kernel(GpmpArgs a, real* __restrict__ means, real* __restrict__ d_th
     extern __shared__ __align__(16) unsigned char gp_lds_raw[];
     __shared__ double csum[64];
     const int l = threadIdx.x;
-    const int sub = PPW == 1 ? 0 : l >> 4, l16 = PPW == 1 ? l : l & 15;       // particle of the wave, lane within its row
+    // particle of the wave, lane within its row.  At two per wave the rows 2 and 3 have no particle: they compute along on row 1's
+    // (the same LDS slice, the same values) and write nothing of their own -- a slice of their own would lie beyond the 2 x per
+    // bytes of the launch, and as particles 2 and 3 of the block they would race the next block for those particles' scratch and costs
+    const int row = l >> 4, l16 = l & 15;
+    const int sub = row < PPW ? row : PPW - 1;
     const int p_raw = blockIdx.x * PPW + sub;
-    const bool valid = p_raw < a.P;
-    const int p = valid ? p_raw : a.P - 1;                // (lanes of a missing particle compute on the last one, write nothing)
+    const bool valid = row < PPW && p_raw < a.P;
+    const int p = p_raw < a.P ? p_raw : a.P - 1;          // (lanes of a missing particle compute on the last one, write nothing)
     const int T = a.T;
     const size_t per = (size_t)2 * T * TS + (size_t)a.n_fields * T * 9;       // doubles of LDS per particle
     double* mu = reinterpret_cast<double*>(gp_lds_raw) + (size_t)sub * per;   // [T][TS] means
@@ -371,7 +372,7 @@ gpmp_thomas_kernel(GpmpArgs a, real* __restrict__ means, real* __restrict__ d_th
     const int r = l16 < D ? l16 : 0;                      // this lane's row (lanes >= D of a row idle along)
     const int k = r % N;
     const bool pos = r < N;
-    const int partner = (PPW == 1 ? 0 : (l & 48)) + (pos ? r + N : r - N);
+    const int partner = (l & 48) + (pos ? r + N : r - N);
     // E2 = -K [[c11, c11 dt + c12], [c12, c12 dt + c22]]  (rows: pos, vel of the LATER waypoint; columns: of the earlier one)
     const double e00 = -a.Kgp * a.c11, e01 = -a.Kgp * (a.c11 * a.dt + a.c12), e10 = -a.Kgp * a.c12, e11 = -a.Kgp * (a.c12 * a.dt + a.c22);
     const double er0 = pos ? e00 : e10, er1 = pos ? e01 : e11;      // this lane's row of E2
@@ -566,34 +567,41 @@ hipError_t launch_gpmp_diag(int dtype, const GpmpArgs& a, double* diag_sum, hipS
 hipError_t launch_gpmp_solve(int dtype, const GpmpArgs& a, void* means, void* d_theta, void* costs,
                              hipStream_t stream, bool cholesky) {
     if (a.P <= 0) return hipSuccess;
-    const size_t lds = ((size_t)2 * a.T * TS + (size_t)a.n_fields * a.T * 9) * sizeof(double);
     // register-resident block-Thomas solve (round 4) for the instantiated joint counts; `cholesky`: round 3's kernel
-    // particles per wave: four (one per row of 16 lanes) while their staging fits the LDS, else two, else one
-    const size_t per_particle = lds;
-    const int ppw = 4 * per_particle <= 150 * 1024 ? 4 : 2 * per_particle <= 150 * 1024 ? 2 : 1;
+    const GpmpSolveLayout lay = gpmp_solve_layout(a.T, a.n_fields);
+    hipError_t e;
 #define THOMAS_L(NN, PP)                                                                                            \
     {                                                                                                               \
         const unsigned grid = (unsigned)((a.P + PP - 1) / PP);                                                      \
-        if (dtype == SGPMP_F64)                                                                                     \
-            hipLaunchKernelGGL((gpmp_thomas_kernel<double, NN, PP>), dim3(grid), dim3(64), PP * per_particle, stream, a,        \
+        if (dtype == SGPMP_F64) {                                                                                   \
+            if ((e = sgpmp_allow_lds(gpmp_thomas_kernel<double, NN, PP>, lay.lds, 512)) != hipSuccess) return e;    \
+            hipLaunchKernelGGL((gpmp_thomas_kernel<double, NN, PP>), dim3(grid), dim3(64), lay.lds, stream, a,      \
                                (double*)means, (double*)d_theta, (double*)costs);                                   \
-        else                                                                                                        \
-            hipLaunchKernelGGL((gpmp_thomas_kernel<float, NN, PP>), dim3(grid), dim3(64), PP * per_particle, stream, a,         \
+        } else {                                                                                                    \
+            if ((e = sgpmp_allow_lds(gpmp_thomas_kernel<float, NN, PP>, lay.lds, 512)) != hipSuccess) return e;     \
+            hipLaunchKernelGGL((gpmp_thomas_kernel<float, NN, PP>), dim3(grid), dim3(64), lay.lds, stream, a,       \
                                (float*)means, (float*)d_theta, (float*)costs);                                      \
+        }                                                                                                           \
         return hipGetLastError();                                                                                   \
     }
 #define THOMAS(NN)                                                                                                  \
     if (!cholesky && a.n == NN) {                                                                                   \
-        if (ppw == 4) THOMAS_L(NN, 4) else if (ppw == 2) THOMAS_L(NN, 2) else THOMAS_L(NN, 1)                       \
+        if (lay.ppw == 4) THOMAS_L(NN, 4) else THOMAS_L(NN, 2)                                                      \
     }
     THOMAS(2) THOMAS(3) THOMAS(6) THOMAS(7)
 #undef THOMAS_L
 #undef THOMAS
-    if (dtype == SGPMP_F64)
+    // gpmp_solve_kernel stages one particle (per_particle bytes) beside 13 312 B of static tiles: the sum passes 64 KiB from three
+    // fields on at T = 128 (8 x 128 x 59 + 13 312 = 73 728 B; with two it is 64 512 B)
+    const size_t lds = lay.per_particle, fixed = (6 * TS * TS + 4 * TS + 64) * sizeof(double);
+    if (dtype == SGPMP_F64) {
+        if ((e = sgpmp_allow_lds(gpmp_solve_kernel<double>, lds, fixed)) != hipSuccess) return e;
         hipLaunchKernelGGL((gpmp_solve_kernel<double>), dim3(a.P), dim3(64), lds, stream, a, (double*)means,
                            (double*)d_theta, (double*)costs);
-    else
+    } else {
+        if ((e = sgpmp_allow_lds(gpmp_solve_kernel<float>, lds, fixed)) != hipSuccess) return e;
         hipLaunchKernelGGL((gpmp_solve_kernel<float>), dim3(a.P), dim3(64), lds, stream, a, (float*)means,
                            (float*)d_theta, (float*)costs);
+    }
     return hipGetLastError();
 }

@@ -462,6 +462,9 @@ hipError_t launch_gpmp_dense_diag(int dtype, const GpmpArgs& a, const GpmpDenseA
 hipError_t launch_gpmp_dense_solve(int dtype, const GpmpArgs& a, const GpmpDenseArgs& da, void* means, void* d_theta,
                                    void* costs, hipStream_t stream) {
     if (a.P <= 0) return hipSuccess;
+    // means and solution [T][16] only (the fields stay in HBM): 32 768 B at SGPMP_MAX_T_GPMP = 128, beside at most 17 648 B of static
+    // tiles and tables -- 50 416 B, below the 64 KiB above which sgpmp_allow_lds would have to raise the kernel's limit
+    static_assert((size_t)2 * SGPMP_MAX_T_GPMP * TS * sizeof(double) + 17648 <= 64 * 1024, "gpmp_dense_solve_kernel: call sgpmp_allow_lds");
     const size_t lds = (size_t)2 * a.T * TS * sizeof(double);
     if (dtype == SGPMP_F64)
         hipLaunchKernelGGL((gpmp_dense_solve_kernel<double>), dim3(a.P), dim3(64), lds, stream, a, da,

@@ -390,8 +390,31 @@ hipError_t launch_ee_grad(int dtype, int n, const CostTerm& term, const ChainDev
 hipError_t launch_field_grad(int dtype, int n, const CostTerm& term, const ChainDev* d_chain, int n_joints,
                              const void* q, long long batch, int traj_T, const void* spheres, int n_spheres,
                              void* value, void* grad, hipStream_t stream);
+// A launch whose dynamic LDS (plus the kernel's static LDS) exceeds 64 KiB has the kernel's dynamic-LDS limit raised first, as the
+// HIP API asks (a gfx950 workgroup may use up to 160 KiB).  Measured on the MI355X: this runtime also accepts such a launch
+// without the call; every launcher makes it all the same, so that no two files of the library disagree about the contract.
+template <typename Kernel>
+static inline hipError_t sgpmp_allow_lds(Kernel kernel, size_t dynamic_bytes, size_t static_bytes = 0) {
+    if (dynamic_bytes + static_bytes <= 64 * 1024) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dynamic_bytes);
+}
+
 // GPMP (gpmp.hip)
 #define SGPMP_MAX_T_GPMP 128
+#define SGPMP_MAX_GPMP_FIELDS 4   // link-field terms of one cost list
+// Particles per wave and dynamic LDS of gpmp_thomas_kernel.  A particle stages per = 8 T (32 + 9 F) bytes (means and solution
+// [T][16] doubles each, F field values [T] and gradients [T][8]); four particles share a wave, one per row of 16 lanes, while
+// 4 per <= 150 KiB (of the 160 KiB a workgroup may use; the kernel adds 512 B of static LDS), else two.  Two always fit: the
+// largest admissible request, T = 128 and F = 4, is per = 69 632 B, 2 per = 139 264 B <= 153 600 B -- a one-per-wave layout would
+// need per > 76 800 B and cannot be reached, so there is none.  Raising either limit below forces a fresh look.
+struct GpmpSolveLayout { int ppw; size_t per_particle, lds; };    // lds = ppw * per_particle
+static inline GpmpSolveLayout gpmp_solve_layout(int T, int n_fields) {
+    static_assert((size_t)2 * 8 * SGPMP_MAX_T_GPMP * (32 + 9 * SGPMP_MAX_GPMP_FIELDS) <= (size_t)150 * 1024,
+                  "gpmp_thomas_kernel: two particles per wave no longer fit the LDS at the largest T and field count");
+    const size_t per = (size_t)8 * T * (32 + 9 * n_fields);
+    const int ppw = 4 * per <= (size_t)150 * 1024 ? 4 : 2;
+    return {ppw, per, ppw * per};
+}
 struct GpmpFieldK {               // one link-field term of the cost list
     double K;                     // 1 / sigma^2
     const void* val;              // [P, T-1]   field values        (context dtype)
@@ -408,7 +431,7 @@ struct GpmpArgs {
     const void* goals;            // [G, d]
     long long rows_per_goal;      // particles per goal
     int n_fields;
-    GpmpFieldK f[4];
+    GpmpFieldK f[SGPMP_MAX_GPMP_FIELDS];
     double delta;
     const double* diag_sum;       // [T*d] sum over all particles of the FIELD part of diag(A^T K A), or null
     double inv_particles;         // 1 / (global particle count)

@@ -752,6 +752,11 @@ class Engine:
         """Name of the solve kernel this thread's last gpmp_solve() launched ("" before the first)."""
         return self.lib.sgpmp_last_gpmp_kernel().decode()
 
+    def last_gpmp_ppw(self):
+        """Particles per wave of that solve: 4 or 2 after gpmp_thomas_kernel, 0 after the other solve kernels and before the first.
+        AttributeError on a library built before the entry point existed (_lib.ADDED_UNDER_THIS_ABI)."""
+        return int(self.lib.sgpmp_last_gpmp_ppw())
+
     def gpmp_solve(self, means, delta, step_size, diag_sum=None, d_theta=None, costs=None):
         """Block-tridiagonal Gauss-Newton solve + in-place update of `means`; -> (d_theta, costs)."""
         self._chk(means, "means")

@@ -25,8 +25,13 @@ def test_header_declares_the_entry_points_under_abi_6():
     assert args == ["sgpmp_ctx* ctx", "int n_sub", "double dt", "double weight", "const double* q_lo", "const double* q_hi",
                     "const double* v_max", "double sigma_limit"]
     assert re.search(r"const char\* sgpmp_last_gpmp_kernel\(void\);", src)
+    assert re.search(r"^int sgpmp_last_gpmp_ppw\(void\);", src, flags=re.M)
     res, argt = _lib.SIGNATURES["sgpmp_gpmp_set_dense"]
     assert len(argt) == len(args) and _lib.SIGNATURES["sgpmp_last_gpmp_kernel"][1] == []
+    import ctypes
+    assert _lib.SIGNATURES["sgpmp_last_gpmp_ppw"] == (ctypes.c_int, [])
+    # an older build of ABI 6 may lack it and still load (_lib.ADDED_UNDER_THIS_ABI); the library of this tree has it
+    assert _lib.ADDED_UNDER_THIS_ABI == {"sgpmp_last_gpmp_ppw"} and _lib.load().sgpmp_last_gpmp_ppw() == 0
     # linearize and solve keep their signatures
     assert len(_lib.SIGNATURES["sgpmp_gpmp_linearize"][1]) == 6 and len(_lib.SIGNATURES["sgpmp_gpmp_solve"][1]) == 8
 
@@ -37,7 +42,7 @@ def test_engine_and_planner_signatures():
     from stoch_gpmp_amd.planner import StochGPMP
     p = inspect.signature(Engine.gpmp_set_dense).parameters
     assert list(p) == ["self", "n_sub", "dt", "weight", "q_limits", "v_limits", "sigma_limit"]
-    assert hasattr(Engine, "last_gpmp_kernel")
+    assert hasattr(Engine, "last_gpmp_kernel") and list(inspect.signature(Engine.last_gpmp_ppw).parameters) == ["self"]
     assert list(inspect.signature(GPMP.set_dense_cost).parameters) == list(inspect.signature(StochGPMP.set_dense_cost).parameters)
     assert GPMP.set_dense_cost is not StochGPMP.set_dense_cost and "NotImplementedError" not in inspect.getsource(GPMP.set_dense_cost)
 
@@ -115,3 +120,42 @@ def test_inputs_make_the_parity_tests_bite(golden, tag, delta, trust):
     _, b, _ = DO.limit_system(means, 7, 3, DO.PANDA["dt"], s["q_lo"], s["q_hi"], s["v_max"], s["sigma_limit"])
     frac = float((b > 0).double().mean())
     assert 0.05 / 3 < frac < 0.25, frac
+
+
+def test_gpmp_solve_layout_over_every_admissible_shape(tmp_path):
+    """csrc/sgpmp_internal.h gpmp_solve_layout -- the function launch_gpmp_solve takes its particles per wave and dynamic LDS from --
+    itself, through tests/host_asan/gpmp_layout.cpp (host-only, -fsanitize=address,undefined): over all traj_len in [2, 128] and
+    0 .. 4 field terms, two or four particles per wave, the request with the kernel's 512 B of static LDS inside a workgroup's
+    160 KiB, four exactly while 4 x 8 T (32 + 9 F) <= 150 KiB; and the rows tests/test_gpu_gpmp_solve.py runs on the GPU."""
+    import shutil
+    import subprocess
+    if not os.path.exists("/opt/rocm/bin/hipcc") or not os.path.exists("/opt/rocm/lib/llvm/bin/clang++"):
+        pytest.skip("no ROCm clang")
+    d = os.path.join(ROOT, "tests", "host_asan")
+    b = str(tmp_path / "build")
+    r = subprocess.run(["make", "-C", d, f"B={b}", os.path.join(b, "gpmp_layout")], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    env = {k: v for k, v in os.environ.items() if not k.startswith(("SGPMP_", "STUB_", "HOST_ASAN"))}
+    env["ASAN_OPTIONS"] = "detect_leaks=1:abort_on_error=0"
+    p = subprocess.run([os.path.join(b, "gpmp_layout")], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0 and "GPMP_LAYOUT_OK" in p.stdout, (p.stdout[-1000:], p.stderr[-4000:])
+    assert "Sanitizer" not in p.stderr and "runtime error" not in p.stderr, p.stderr[-4000:]
+    shutil.rmtree(b, ignore_errors=True)
+    lines = p.stdout.split("\n")
+    assert lines[0] == "LIMITS 128 4"
+    rows = {}
+    for ln in lines[1:]:
+        v = ln.split()
+        if len(v) == 5:
+            rows[(int(v[0]), int(v[1]))] = tuple(int(x) for x in v[2:])
+    assert sorted(rows) == [(T, F) for T in range(2, 129) for F in range(5)]
+    for (T, F), (ppw, per, lds) in rows.items():
+        assert per == 8 * T * (32 + 9 * F) and lds == ppw * per, (T, F)
+        assert ppw in (2, 4) and ppw * per + 512 <= 160 * 1024, (T, F, ppw)
+        assert (ppw == 4) == (4 * per <= 150 * 1024), (T, F, ppw)
+    # planar (one field), Panda (two fields), no field: (ppw, request)
+    want = {(49, 1): (4, 64288), (50, 1): (4, 65600), (117, 1): (4, 153504), (118, 1): (2, 77408), (128, 1): (2, 83968),
+            (40, 2): (4, 64000), (41, 2): (4, 65600), (96, 2): (4, 153600), (97, 2): (2, 77600),
+            (64, 0): (4, 65536), (65, 0): (4, 66560), (128, 4): (2, 139264)}
+    for k, (ppw, lds) in want.items():
+        assert (rows[k][0], rows[k][2]) == (ppw, lds), (k, rows[k])

@@ -1509,31 +1509,7 @@ def test_store_free_row_counts_travel_with_the_state():
 # the Panda only; another chain's code is generated by the host (csrc/gen/chain_codegen.py) and compiled by the library at
 # run time (csrc/chain_rtc.hip, hiprtc): these tests put two such robots on the fused launch and the chunked sweep and
 # check them against the oracle running oracle/fk.py on the SAME chain.
-def _arm7():
-    """A 7-DoF arm that is NOT the Panda: its link lengths / offsets changed, another flange."""
-    from stoch_gpmp_amd.robots.panda_chain import PANDA_CHAIN
-    ch = [(nm, kind, tuple(rpy), list(xyz)) for nm, kind, rpy, xyz in PANDA_CHAIN]
-    ch[0][3][2] = 0.36; ch[2][3][1] = -0.29; ch[3][3][0] = 0.07; ch[4][3][0] = -0.07; ch[4][3][1] = 0.41; ch[6][3][0] = 0.1
-    ch[7][3][2] = 0.15                                   # a longer flange ...
-    ch[8] = (ch[8][0], ch[8][1], (0.0, 0.0, 0.3), ch[8][3])          # ... turned differently
-    return [(nm, kind, tuple(rpy), tuple(xyz)) for nm, kind, rpy, xyz in ch]
-
-
-def _arm6():
-    """A 6-DoF arm (UR-like proportions): six revolute joints and a tool flange."""
-    h = 1.57079632679
-    return [("j1", "revolute", (0.0, 0.0, 0.0), (0.0, 0.0, 0.1625)), ("j2", "revolute", (h, 0.0, 0.0), (0.0, 0.0, 0.0)),
-            ("j3", "revolute", (0.0, 0.0, 0.0), (-0.425, 0.0, 0.0)), ("j4", "revolute", (0.0, 0.0, 0.0), (-0.3922, 0.0, 0.1333)),
-            ("j5", "revolute", (h, 0.0, 0.0), (0.0, -0.0997, 0.0)), ("j6", "revolute", (-h, 0.0, 0.0), (0.0, 0.0996, 0.0)),
-            ("tool", "fixed", (0.0, 0.0, 0.0), (0.0, 0.0, 0.12))]
-
-
-def _arm_config(chain):
-    n = sum(1 for j in chain if j[1] == "revolute")
-    c = dict(SC.PANDA, n_dof=n)
-    if n == 6:
-        c.update(start_q=[0.1, -1.2, 1.4, -0.4, 0.8, 0.2], goal_q=[0.9, -0.7, 0.9, 0.3, 1.1, -0.4])
-    return c, n
+from tests.arm_chains import arm6 as _arm6, arm7 as _arm7, arm_config as _arm_config  # noqa: E402  (shared with test_gpu_gpmp_solve.py)
 
 
 @pytest.mark.parametrize("arm,field_type", [("arm7", "rbf"), ("arm7", "sdf"), ("arm6", "rbf")])
