@@ -181,6 +181,8 @@ void sgpmp_destroy(sgpmp_ctx* ctx);
  * no folded end-effector term, 512 to 1023 particles and at most 256 samples per particle, where it measured faster -- applies;
  * -1: update_kernel_quad wherever it can run; 0: the rule.  Bit-identical.  PROCESS-WIDE, unlike every other switch: it holds for
  * all contexts of the process; SGPMP_UPDATE_WIDE is read once per process, by the first sgpmp_create),
+ * fused_generic (fused_step_kernel's generic instantiation, which reads the cost program at run time, even where the one with the
+ * four-term program compiled in applies -- sgpmp_last_fused_variant; bit-identical),
  * pipe_split (1..15) and k3_blocks (count).  (The launches that measured slower -- tail_update, small_step, planar_slabs,
  * wave_groups, fused_pipe -- were removed in round 5; DESIGN.md 8 keeps their numbers and the commit that last held them.)
  * No reference counterpart. */
@@ -189,6 +191,11 @@ int sgpmp_set_option(sgpmp_ctx* ctx, const char* name, long long value);
  * (static string; "" before the first launch).  For bench.py's roofline label and the tests that
  * must prove which kernel they exercised. */
 const char* sgpmp_last_cost_kernel(sgpmp_ctx* ctx);
+/* Which instantiation of fused_step_kernel the last fused launch of sgpmp_step / sgpmp_optimize was.  0: the generic one (and every
+ * other fused launch).  1, 2: the one with the cost program compiled in -- exactly GP term with start prior, goal prior, self term
+ * and sphere term, a storing step on the launch's grid of 8 samples x 16 waypoints; 1 without softmax partials (no_dense_partials),
+ * 2 with the partials buffer armed (the default).  Same samples and costs, bit for bit. */
+int sgpmp_last_fused_variant(sgpmp_ctx* ctx);
 
 /* K1. GP-prior precision blocks + reverse block-Cholesky, fp64, one launch.
  * Replaces GPFactor.calc_phi/calc_Q_inv (gp_factor.py:36-52), UnaryFactor.K (unary_factor.py:19),

@@ -75,6 +75,7 @@ SIGNATURES = {
     "sgpmp_set_step_mode_stats": (_I, [_P, _P]),
     "sgpmp_mode_stats_wait": (_I, [_P, _P]),
     "sgpmp_last_cost_kernel": (C.c_char_p, [_P]),
+    "sgpmp_last_fused_variant": (_I, [_P]),
     "sgpmp_pipeline_begin": (_I, [_P, _P]),
     "sgpmp_pipeline_end": (_I, [_P, _P]),
     "sgpmp_pipeline_split_steps": (C.c_longlong, [_P]),
@@ -140,6 +141,8 @@ class SgpmpError(RuntimeError):
 # through SGPMP_LIB_PATH, a test-hooks build that was not rebuilt -- lacks them and still loads; everything else stays mandatory.
 # tests/test_cpu_host.py holds the library of THIS tree to every declared symbol, these included.
 ADDED_UNDER_THIS_ABI = frozenset({"sgpmp_last_gpmp_ppw"})
+# ... and the queries added since (tests/test_cpu_gpmp_dense.py holds the set above to its one member): same rule
+ADDED_LATER_UNDER_THIS_ABI = frozenset({"sgpmp_last_fused_variant"})
 
 
 def load():
@@ -154,7 +157,7 @@ def load():
             "stoch_gpmp_amd has no CPU/torch fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
-        if name in ADDED_UNDER_THIS_ABI and not hasattr(lib, name):
+        if name in ADDED_UNDER_THIS_ABI | ADDED_LATER_UNDER_THIS_ABI and not hasattr(lib, name):
             continue                     # (an older build of this ABI: calling it there raises AttributeError)
         fn = getattr(lib, name)          # AttributeError if the ABI symbol is missing
         fn.restype = res

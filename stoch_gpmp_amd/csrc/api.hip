@@ -80,6 +80,7 @@ struct sgpmp_ctx {
     const void* isw_means;        // the means buffer they belong to
     double isw_temperature;
     const char* last_cost_kernel; // name of the cost-sweep kernel the dispatcher picked last
+    int last_fused_variant = 0;   // StepPlan::full of the last fused launch (sgpmp_last_fused_variant)
     StepPipe pipe;                // two-chain execution of consecutive steps (sgpmp_pipeline_begin / _end)
     // the update inside fused_planar_seg_kernel (store-free steps, S = 64): per-launch finished-particle counters and
     // statistics accumulators ([0]: whole range / first half, [1]: second half of a two-chain step); zero between
@@ -126,7 +127,7 @@ static const struct { const char* name; int SgpmpToggles::*flag; } kToggleNames[
     {"no_chunked_sweep", &SgpmpToggles::no_chunked_sweep}, {"no_step_pipeline", &SgpmpToggles::no_step_pipeline},
     {"comm_packet_event", &SgpmpToggles::comm_packet_event}, {"no_planar_seg", &SgpmpToggles::no_planar_seg}, {"planar_store_free", &SgpmpToggles::planar_store_free}, {"no_planar_tail", &SgpmpToggles::no_planar_tail}, {"no_persist_planar", &SgpmpToggles::no_persist_planar},
     {"no_small_step", &SgpmpToggles::no_small_step}, {"no_ee_fold", &SgpmpToggles::no_ee_fold}, {"no_dense_partials", &SgpmpToggles::no_dense_partials}, {"gpmp_cholesky", &SgpmpToggles::gpmp_cholesky},
-    {"f64_fields_f32", &SgpmpToggles::f64_fields_f32},
+    {"f64_fields_f32", &SgpmpToggles::f64_fields_f32}, {"fused_generic", &SgpmpToggles::fused_generic},
 };
 
 static void toggles_from_env(SgpmpToggles& tg) {
@@ -252,6 +253,7 @@ extern "C" int sgpmp_set_option(sgpmp_ctx* c, const char* name, long long value)
 }
 
 extern "C" const char* sgpmp_last_cost_kernel(sgpmp_ctx* c) { return c ? c->last_cost_kernel : ""; }
+extern "C" int sgpmp_last_fused_variant(sgpmp_ctx* c) { return c ? c->last_fused_variant : 0; }
 
 // ---------------------------------------------------------------------------------- collectives
 #define COMMCHK(expr)                                                                        \
@@ -1415,6 +1417,7 @@ static int run_range(sgpmp_ctx* c, const StepPlan& plan, const StepArgs& a, size
         io.dense.weights = wh; io.dense.grad = gh; io.dense.means_prev = mph; io.dense.step_size = a.step_size;
         HIPCHK(launch_fused_step(plan, io));
         c->last_cost_kernel = plan.kernel;
+        c->last_fused_variant = plan.full;
         launches += 1;
         if (plan.ee == STEP_EE_FOLD) eet = ee_term_to_fold(c);
         for (int i = 0; plan.ee == STEP_EE_LAUNCH && i < c->h_prog.n_terms; ++i)

@@ -193,10 +193,19 @@ hipError_t launch_fused_step(const StepPlan& plan, const StepIo& io) {
         return hipGetLastError();
     }
     // S, T off the launch's grid of 8 rows x 16 waypoints: the instantiation with the masks (fused_step.inc: RAG)
-#define FUSED_LAUNCH(FT_, RAG_) hipExtLaunchKernelGGL((fused_step_kernel<CCp::N, CCp, FT_, RAG_>), dim3((unsigned)blocks), dim3(256), (unsigned)dyn + SGPMP_FUSED_EXTRA_LDS, stream, (hipEvent_t) nullptr, (hipEvent_t) nullptr, 0u, a, F, fs)
-    if (ft == SGPMP_FIELD_RBF) { if (rag) FUSED_LAUNCH(SGPMP_FIELD_RBF, true); else FUSED_LAUNCH(SGPMP_FIELD_RBF, false); }
-    else if (ft == SGPMP_FIELD_SDF) { if (rag) FUSED_LAUNCH(SGPMP_FIELD_SDF, true); else FUSED_LAUNCH(SGPMP_FIELD_SDF, false); }
-    else { if (rag) FUSED_LAUNCH(SGPMP_FIELD_OCCUPANCY, true); else FUSED_LAUNCH(SGPMP_FIELD_OCCUPANCY, false); }
+#define FUSED_LAUNCH(...) hipExtLaunchKernelGGL((fused_step_kernel<CCp::N, CCp, __VA_ARGS__>), dim3((unsigned)blocks), dim3(256), (unsigned)dyn + SGPMP_FUSED_EXTRA_LDS, stream, (hipEvent_t) nullptr, (hipEvent_t) nullptr, 0u, a, F, fs)
+    // the four-term program compiled in (fused_step.inc: FULL; step_plan.hip: fused_full_variant -- what the plan says must hold HERE,
+    // or the launch would ignore a term or an argument it was given)
+    const int full = plan.full;
+    if (full != 0 && (rag || fs.nostore || (full == 1) != (fs.part == nullptr) || !F.has_gp || !(F.gp.flags & SGPMP_FLAG_GP_START) ||
+                      !F.has_goal || !F.has_self || !F.has_sph || F.has_grid))
+        return hipErrorInvalidValue;
+#define FUSED_FIELD(FT_) do { if (full == 1) FUSED_LAUNCH(FT_, false, 1); else if (full == 2) FUSED_LAUNCH(FT_, false, 2); \
+                              else if (rag) FUSED_LAUNCH(FT_, true); else FUSED_LAUNCH(FT_, false); } while (0)
+    if (ft == SGPMP_FIELD_RBF) FUSED_FIELD(SGPMP_FIELD_RBF);
+    else if (ft == SGPMP_FIELD_SDF) FUSED_FIELD(SGPMP_FIELD_SDF);
+    else FUSED_FIELD(SGPMP_FIELD_OCCUPANCY);
+#undef FUSED_FIELD
 #undef FUSED_LAUNCH
     return hipGetLastError();
 }

@@ -37,6 +37,8 @@
 #endif
 
 template <bool B> struct BoolC { static constexpr bool value = B; };
+// a has_* flag of the cost program: read at run time, or a compile-time fact (chunked_body: FULL)
+template <int FULL> __device__ __forceinline__ int prog_has(int flag) { if constexpr (FULL != 0) return 1; else return flag; }
 
 // x^2 + y^2 + z^2 in ONE evaluation order.  Written as a sum of three products hipcc is free to decide which product becomes
 // the addend of which fma -- and decided differently from one instantiation of chunked_body to another (round 5: the small-step
@@ -154,9 +156,19 @@ struct FusedArgs {
 // per chunk, the state handed on through LDS), then x = mu + y, the stores and the cost terms of all chunks side by side; wave 0
 // adds the chunks' cost shares IN CHUNK ORDER.  Same counters, same expressions, same order of every sum: samples and costs are
 // bit-identical to the one-wave-per-item launch (tests/test_gpu_planner.py::test_small_step_launch_*).
-template <int N, class CC, int FT, bool SWEEP, bool RAG = false, bool LAT = false>
+// FULL (round 17): the cost program and the launch's mode as compile-time facts, for the one program every Panda example and the
+// headline run -- GP term with start prior, goal prior, self term and sphere term all present (prog_has), a storing launch
+// (nostore == 0).  The generic instantiation keeps every alternative alive in SGPRs through the item: 84 spilled, 217
+// v_readlane / v_writelane, 12 of them inside the chunk loop -- vector instructions, on a launch bound by vector issue.
+// FULL = 1: no softmax partials either (part == nullptr); FULL = 2: the partials buffer stays a run-time value (default contexts
+// arm it for every step on the grid).  The shift-or-divide choice of the particle and goal index stays at run time (as
+// compile-time facts: 30 -> 24 spilled SGPRs, and particles of 24 samples would fall back to the generic kernel).  Same
+// expressions in the same order: step_plan.hip fused_full_variant selects, tests/test_gpu_fused_full.py holds samples and costs to
+// the generic instantiation's bits, profiles/r17/fused_full.txt has the counts.
+template <int N, class CC, int FT, bool SWEEP, bool RAG = false, bool LAT = false, int FULL = 0>
 __device__ __forceinline__ void chunked_body(const CostArgs<float>& a, const FlatProg<float>& F, const FusedArgs& s) {
     static_assert(!LAT || !SWEEP, "the small-step schedule exists for the fused launch");
+    static_assert(!FULL || (!SWEEP && !RAG && !LAT), "the compiled-in program exists for the fused launch on the 8 x 16 grid");
     constexpr int D = 2 * N, TC = SGPMP_FUSED_TC, SPW = SGPMP_FUSED_SPW;
     constexpr int HEAD = ((D + 3) / 4) * 4;              // floats in front of a row's chunk: [pad | carry waypoint]
     constexpr int PITCH = HEAD + TC * D;                 // floats per tile row (16-byte multiple; 240 for d = 14)
@@ -224,8 +236,8 @@ __device__ __forceinline__ void chunked_body(const CostArgs<float>& a, const Fla
     // Few spheres and goals (the usual case) come in through the SCALAR cache: every new wave pays this prologue, and as
     // vector loads its two dozen words queued behind the launch's sample stores for ~7 us (tools/fused_stamps.py: 17 k
     // of a wave's 88 k cycles, round 4); the constant cache path does not share that queue and the table is hot in it.
-    const int ng_ = F.has_goal ? F.goal.dim0 : 0;
-    const bool gp_start_ = F.has_gp && (F.gp.flags & SGPMP_FLAG_GP_START);
+    const int ng_ = prog_has<FULL>(F.has_goal) ? F.goal.dim0 : 0;
+    const bool gp_start_ = prog_has<FULL>(F.has_gp) && (FULL || (F.gp.flags & SGPMP_FLAG_GP_START));
     const bool scalar_prologue = SGPMP_FUSED_SCALAR_PROLOGUE && a.n_spheres <= 16 && ng_ <= 3;
     auto sphere_row = [&](int o, float cx, float cy, float cz, float r) {
         if (FT == SGPMP_FIELD_RBF) {
@@ -314,7 +326,7 @@ __device__ __forceinline__ void chunked_body(const CostArgs<float>& a, const Fla
     PSTAMP(1);
     auto static_sphere_sum = [&]() {
     float sph_static = 0.f;
-    if (F.has_sph) {
+    if (prog_has<FULL>(F.has_sph)) {
         float q0[N], P0[CC::NREP][3];
 #pragma unroll
         for (int k = 0; k < N; ++k) q0[k] = 0;
@@ -372,7 +384,7 @@ __device__ __forceinline__ void chunked_body(const CostArgs<float>& a, const Fla
 #define SGPMP_FUSED_FRESH_LANE 0
 #endif
     auto fresh_lane = [&]() { int l = lane; if (SGPMP_FUSED_FRESH_LANE) asm volatile("" : "+v"(l)); return l; };
-    const bool gp_start = F.has_gp && (F.gp.flags & SGPMP_FLAG_GP_START);
+    const bool gp_start = prog_has<FULL>(F.has_gp) && (FULL || (F.gp.flags & SGPMP_FLAG_GP_START));
     const size_t M = (size_t)T * D;
 
     const long long nitems = SWEEP ? a.batch / SPW : s.nitems;
@@ -402,12 +414,12 @@ __device__ __forceinline__ void chunked_body(const CostArgs<float>& a, const Fla
         const long long b0 = !RAG ? item * SPW : (long long)p * s.S + (long long)g * SPW;
         const int nv = !RAG ? SPW : (s.S - (int)g * SPW < SPW ? s.S - (int)g * SPW : SPW);
         const unsigned grow = (unsigned)(a.batch_offset + b0);
-        const unsigned gidx = !F.has_goal ? 0u : a.rpg_shift >= 0 ? grow >> a.rpg_shift : grow / (unsigned)F.goal.rows_per_goal;
+        const unsigned gidx = !prog_has<FULL>(F.has_goal) ? 0u : a.rpg_shift >= 0 ? grow >> a.rpg_shift : grow / (unsigned)F.goal.rows_per_goal;
         const float* const mu = SWEEP ? a.trajs : s.means + (size_t)p * M;
         const bool use_is = !SWEEP || a.isw != nullptr;
         const float* const isw = use_is ? a.isw + (size_t)p * (T + 1) * D : a.trajs;
         // (wave-uniform; the scalar load is issued here, a whole noise phase ahead of its first use)
-        const bool store_rows = SWEEP || !s.nostore || (s.nnz_prev != nullptr && as_const(s.nnz_prev)[p] > s.store_threshold);
+        const bool store_rows = SWEEP || FULL || !s.nostore || (s.nnz_prev != nullptr && as_const(s.nnz_prev)[p] > s.store_threshold);
         float yp = 0.f, yv = 0.f;                        // recurrence state (perturbation of position / velocity)
         f2 run = f2{0.f, 0.f};
         FSTAMP_DECL;
@@ -723,7 +735,7 @@ __device__ __forceinline__ void chunked_body(const CostArgs<float>& a, const Fla
                     tot += ds * ds * F.gp.K2;
                 }
             }
-            if (t0 + TC >= T && F.has_goal) {
+            if (t0 + TC >= T && prog_has<FULL>(F.has_goal)) {
                 if (tc < D) {
                     const float* r0 = tile + (2 * jc) * PITCH + HEAD + (T - 1 - t0) * D + tc;
                     const f2 dg = f2{r0[0], r0[PITCH]} - unl[(gidx + 1) * 16 + tc];
@@ -755,7 +767,7 @@ __device__ __forceinline__ void chunked_body(const CostArgs<float>& a, const Fla
             {
                 // GP factors (gp_factor.py:54-67) and the importance-sampling product (planner.py:233-236)
                 // on e_t = x_t - Phi x_{t-1}; for t = 0, x_{-1} = 0 makes e_0 = x_0, the first block of A x
-                const float dtg = F.has_gp ? F.gp.dt : a.is_dt;
+                const float dtg = prog_has<FULL>(F.has_gp) ? F.gp.dt : a.is_dt;
                 f2 pp = f2{0.f, 0.f}, pv = pp, vv = pp, dis = pp;
 #pragma unroll
                 for (int k = 0; k < N; ++k) {
@@ -764,7 +776,7 @@ __device__ __forceinline__ void chunked_body(const CostArgs<float>& a, const Fla
                     pp += ep * ep; pv += ep * ev; vv += ev * ev;
                     dis += ep * w[k] + ev * w[N + k];
                 }
-                if (F.has_gp && inner)
+                if (prog_has<FULL>(F.has_gp) && inner)
                     tot += (pp * F.gp.c11 + pv * (2.f * F.gp.c12) + vv * F.gp.c22) * F.gp.K;
                 if (!RAG || t0 + TC <= T) tot += dis;                    // (wave-uniform)
                 else tot += f2{t < T ? dis.x : 0.f, t < T ? dis.y : 0.f};
@@ -780,10 +792,10 @@ __device__ __forceinline__ void chunked_body(const CostArgs<float>& a, const Fla
             FSTAMP(2);
             f2 part = f2{0.f, 0.f};
 #ifndef SGPMP_FUSED_NO_FK
-            if (F.has_self || F.has_sph) {
+            if (prog_has<FULL>(F.has_self) || prog_has<FULL>(F.has_sph)) {
                 f2 Pq[CC::NREP][3];
                 CC::template fk_snapped<f2, O>(q, Pq);
-                if (F.has_self) {
+                if (prog_has<FULL>(F.has_self)) {
                     const float kk = F.self.K2 * (float)SGPMP_LOG2E;
                     f2 f = f2{F.self.selfc, F.self.selfc};
 #pragma unroll
@@ -794,7 +806,7 @@ __device__ __forceinline__ void chunked_body(const CostArgs<float>& a, const Fla
                     }
                     if (inner) part += f * F.self.K;
                 }
-                if (F.has_sph && FT != SGPMP_FIELD_RBF) {
+                if (prog_has<FULL>(F.has_sph) && FT != SGPMP_FIELD_RBF) {
                     const bool clamp = (F.sph.flags & SGPMP_FLAG_SDF_CLAMP) != 0;
                     f2 f = f2{sph_static, sph_static};
                     for (int o = 0; o < a.n_spheres; ++o) {
@@ -829,7 +841,7 @@ __device__ __forceinline__ void chunked_body(const CostArgs<float>& a, const Fla
                     }
                     if (inner) part += f * F.sph.K;
                 }
-                if (F.has_sph && FT == SGPMP_FIELD_RBF) {
+                if (prog_has<FULL>(F.has_sph) && FT == SGPMP_FIELD_RBF) {
                     f2 pp[CC::NREP];
 #pragma unroll
                     for (int l = 0; l < CC::NREP; ++l)
@@ -1012,7 +1024,7 @@ __device__ __forceinline__ void chunked_body(const CostArgs<float>& a, const Fla
         // memory -- this wave's own write-through stores, waited for -- 16 bytes per lane and row: 32 loads and ~300 vector
         // instructions per item, against the re-read of all S rows by update_kernel.  Taken only for particles whose previous
         // update found the weight spread (a per-particle device-side count, no host round trip): one-hot weights change nothing.
-        if (!SWEEP && s.part != nullptr) {
+        if (!SWEEP && FULL != 1 && s.part != nullptr) {
             const unsigned prev = as_const(s.nnz_prev)[p];                 // wave-uniform: scalar load
             if (prev > s.nnz_threshold && store_rows) {                    // (store_rows: implied by the host's thresholds; the re-read below needs the rows)
                 // the 8 costs of the item to every lane (lanes 0, 16, 32, 48 hold rows 2 j, 2 j + 1)
@@ -1063,6 +1075,18 @@ __attribute__((amdgpu_num_vgpr(SGPMP_FUSED_NUM_VGPR)))
 #endif
 fused_step_kernel(const CostArgs<float> a, const FlatProg<float> F, const FusedArgs s) {
     chunked_body<N, CC, FT, false, RAG>(a, F, s);
+}
+// ... with the four-term program compiled in (chunked_body: FULL = 1, 2).  An overload, so that the generic instantiations keep
+// their symbols.
+template <int N, class CC, int FT, bool RAG, int FULL>
+__global__ void __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(SGPMP_FUSED_WAVES_RS, SGPMP_FUSED_WAVES_RS)))
+#ifdef SGPMP_FUSED_NUM_VGPR
+__attribute__((amdgpu_num_vgpr(SGPMP_FUSED_NUM_VGPR)))
+#endif
+fused_step_kernel(const CostArgs<float> a, const FlatProg<float> F, const FusedArgs s) {
+    static_assert(FULL == 1 || FULL == 2, "the generic kernel is the four-parameter template");
+    chunked_body<N, CC, FT, false, RAG, false, FULL>(a, F, s);
 }
 
 // the same step for a launch of few items (chunked_body: LAT): one workgroup per item.  The recurrence's halves keep a chunk's

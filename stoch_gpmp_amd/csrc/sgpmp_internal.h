@@ -129,6 +129,7 @@ struct SgpmpToggles {
     int f64_fields_f32;       // SGPMP_F64_FIELDS_F32       fp64 steps (fused_step_f64_kernel) evaluate the LINK fields -- forward kinematics, self-distance and sphere fields -- on the packed-fp32 code of the fp32 launches, from the fp64 waypoint rounded to fp32; samples, means, GP / goal-prior / importance-sampling terms stay fp64.  Opt-in: the collision part of a cost then carries fp32's ~1e-6 relative error (~1e-9 of a total cost at the reference's hyper-parameters)
     int no_persist_planar;    // SGPMP_NO_PERSIST_PLANAR    sgpmp_optimize runs the store-free iterations of a planar S = 64 problem as one launch each (round 5) instead of ONE launch for all of them (fused_planar_seg.inc: PERSIST)
     int no_small_step;        // SGPMP_NO_SMALL_STEP        small steps through fused_step_kernel (one wave per item) instead of fused_step_small_kernel (one workgroup per item)
+    int fused_generic;        // SGPMP_FUSED_GENERIC        fused_step_kernel's generic instantiation (the cost program read at run time) even where the one with the four-term program compiled in applies (fused_step.inc: FULL)
     long long persist_max_iters;  // SGPMP_PERSIST_MAX_ITERS    iterations ONE launch of fused_planar_seg_kernel<.., PERSIST> runs at most (0: 2048 -- ~25 ms at BASELINE configs[1]: a launch must stay far below the driver's hang detection); longer calls take several such launches
     long long small_step_items;   // SGPMP_SMALL_STEP_ITEMS     items (groups of 8 samples) up to which a step counts as small (0: default 512 -- two workgroups per CU -- for shapes on the launch's 8 x 16 grid, 256 for the others)
     long long store_free_min_bytes;   // SGPMP_STORE_FREE_MIN_BYTES  a store-free step that REGENERATES rows in update_kernel is taken when one waypoint of all the step's samples (P S 2n floats) has at least this many bytes (0: the measured break-even, SGPMP_STORE_FREE_BREAK_EVEN; 1: always)
@@ -331,6 +332,7 @@ struct StepPlan {
     hipFunction_t rtc_fn;         // STEP_CHAIN_RTC: the kernel
     long long block_cap;          // workgroups of the grid-stride launches at most
     bool partials;                // the launch leaves softmax partials for the update (FusedDenseHost::part must be there)
+    int full;                     // chain code: fused_step_kernel's instantiation (fused_full_variant; 0: the generic one)
     int regen_recipe;             // store-free step whose update_kernel regenerates rows: RegenHost::recipe (0: the step stores, or has no update_kernel)
     bool update_in_launch;        // the launch updates its particles itself: no update_kernel behind it
     int max_iters;                // iterations one such launch may carry (1, or the PERSIST cap)
@@ -340,6 +342,11 @@ struct StepPlan {
 };
 StepPlan plan_step(const StepShape& shape, const StepWants& wants, const PriorDev& prior, const CostProgram& prog,
                    const ChainDev& chain, const SgpmpToggles& tg);
+// Which instantiation of fused_step_kernel a chain-code plan launches (fused_step.inc: FULL).  0: the generic one, which reads the
+// cost program at run time.  1, 2: the program compiled in -- exactly GP term with start prior + goal prior + self term + sphere
+// term, a storing launch of the library's own chain code on the 8 x 16 grid, one wave per item; 1 without softmax partials, 2 with
+// the partials buffer armed.  A function of its arguments alone (tests/host_asan/fused_full_table.cpp walks it).
+int fused_full_variant(const StepPlan& plan, const CostProgram& prog, const SgpmpToggles& tg);
 // what update_kernel is told behind a launch of this plan (recipe 0: nothing to regenerate)
 static inline RegenHost plan_regen(const StepPlan& plan, const PriorDev& prior, uint64_t seed, uint64_t draw, unsigned store_threshold) {
     RegenHost r = {};

@@ -40,6 +40,24 @@ static bool flat_fits(const CostProgram& prog, const PriorDev& prior, int S, Fla
     return true;
 }
 
+int fused_full_variant(const StepPlan& plan, const CostProgram& prog, const SgpmpToggles& tg) {
+    if (tg.fused_generic || plan.family != STEP_CHAIN || plan.ragged || plan.small || plan.regen_recipe != 0) return 0;
+    // exactly the four terms, one of each kind (an end-effector term is a fifth; the grid term never reaches a chain plan)
+    if (prog.n_terms != 4 || prog.n_ee != 0) return 0;
+    bool gp = false, goal = false, self = false, sph = false;
+    for (int i = 0; i < prog.n_terms; ++i) {
+        const CostTerm& t = prog.terms[i];
+        if (t.n_interp > 0) return 0;
+        if (t.kind == SGPMP_COST_GP && !gp) gp = (t.flags & SGPMP_FLAG_GP_START) != 0;
+        else if (t.kind == SGPMP_COST_GOAL_PRIOR && !goal) goal = true;
+        else if (t.kind == SGPMP_COST_SELF && !self) self = true;
+        else if (t.kind == SGPMP_COST_SPHERES && !sph) sph = true;
+        else return 0;
+    }
+    if (!(gp && goal && self && sph)) return 0;
+    return plan.partials ? 2 : 1;
+}
+
 StepPlan plan_step(const StepShape& shape, const StepWants& wants, const PriorDev& prior, const CostProgram& prog,
                    const ChainDev& chain, const SgpmpToggles& tg) {
     using CCp = ChainCode_panda;
@@ -148,6 +166,7 @@ StepPlan plan_step(const StepShape& shape, const StepWants& wants, const PriorDe
                 p.partials = !tg.no_dense_partials && (T * 2 * n) % 4 == 0;
                 p.regen_recipe = regen(1);
             }
+            p.full = fused_full_variant(p, prog, tg);
         }
     }
     // The step's end-effector goal term goes INTO update_kernel (update_common.h: EeFold) when it is the only one and the kernel's

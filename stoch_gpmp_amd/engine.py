@@ -128,6 +128,11 @@ class Engine:
         """Launches that ran several iterations of an optimize(opt_iters = K) call each (planar problems, 64 samples per particle)."""
         return int(self.lib.sgpmp_multi_iteration_launches(self._ctx))
 
+    def last_fused_variant(self):
+        """Which instantiation of fused_step_kernel the last fused launch was (include/sgpmp.h: sgpmp_last_fused_variant):
+        0 generic, 1 / 2 the four-term program compiled in (without / with the softmax partials armed)."""
+        return int(self.lib.sgpmp_last_fused_variant(self._ctx))
+
     def last_cost_kernel(self):
         """Name of the cost-sweep kernel the dispatcher picked at the last launch."""
         return self.lib.sgpmp_last_cost_kernel(self._ctx).decode()
