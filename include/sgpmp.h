@@ -761,6 +761,12 @@ const char* sgpmp_last_gpmp_kernel(void);
 /* Particles per wave of that solve: 4 or 2 after "gpmp_thomas_kernel" (four while 4 x 8 T (32 + 9 F) bytes of staging, F the number
  * of link-field terms, fit 150 KiB of LDS; else two), 0 after the other two kernels and before the first solve. */
 int sgpmp_last_gpmp_ppw(void);
+/* Kernel and launch parameters of the sampler launch this thread last enqueued (sgpmp_sample, and the sampler launch of a step
+ * that is not fused): "sample_iso_kernel<VW=2>" or "<VW=4>" (store width in elements), "sample_iso_small_kernel<NC=7,spb=8,tc=64>"
+ * (compiled-in dof count or 0, samples per workgroup, waypoints per chunk), "sample_dense_kernel", with "(per-mode)" appended
+ * when each mode has factors of its own (sgpmp_set_prior_blocks); "" before the first.  For the tests that must prove which
+ * branch of the dispatch they exercised.  Valid until this thread's next call of this function. */
+const char* sgpmp_last_sample_kernel(void);
 
 /* Kernel timing helper for bench.py: elapsed ms between two events recorded on `stream`
  * (HIP events on the stream the kernels run on). */

@@ -122,6 +122,7 @@ SIGNATURES = {
     "sgpmp_gpmp_set_dense": (_I, [_P, _I, _D, _D, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), _D]),
     "sgpmp_last_gpmp_kernel": (C.c_char_p, []),
     "sgpmp_last_gpmp_ppw": (C.c_int, []),
+    "sgpmp_last_sample_kernel": (C.c_char_p, []),
     "sgpmp_event_create": (_I, [C.POINTER(_P)]),
     "sgpmp_event_record": (_I, [_P, _P]),
     "sgpmp_event_elapsed_ms": (_I, [_P, _P, C.POINTER(C.c_float)]),
@@ -142,7 +143,7 @@ class SgpmpError(RuntimeError):
 # tests/test_cpu_host.py holds the library of THIS tree to every declared symbol, these included.
 ADDED_UNDER_THIS_ABI = frozenset({"sgpmp_last_gpmp_ppw"})
 # ... and the queries added since (tests/test_cpu_gpmp_dense.py holds the set above to its one member): same rule
-ADDED_LATER_UNDER_THIS_ABI = frozenset({"sgpmp_last_fused_variant"})
+ADDED_LATER_UNDER_THIS_ABI = frozenset({"sgpmp_last_fused_variant", "sgpmp_last_sample_kernel"})
 
 
 def load():

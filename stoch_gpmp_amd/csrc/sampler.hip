@@ -10,6 +10,7 @@
 // G_t = g_t (x) I_n and H_t = h_t (x) I_n with 2x2 g_t, h_t): one thread per (sample, dof) runs a
 // 7-FMA recurrence on (position_k, velocity_k); coefficients are wave-uniform scalar loads.
 // Dense path (user-supplied Q_c_inv): one thread per sample carries the full d-vector.
+#include <cstdio>
 #include <cstdlib>
 #include "sgpmp_internal.h"
 #include "rng.h"
@@ -365,6 +366,21 @@ sample_dense_kernel(int n, int T, int S, const real* __restrict__ G, const real*
     }
 }
 
+// Which kernel this thread's last launch_sample enqueued, with its launch parameters (sgpmp_last_sample_kernel): the tests that
+// hold a branch of the dispatch below to the oracle must prove they reached it.  The launch path stores four integers; the text is
+// made when somebody asks.
+struct SampleRecord { int kind, a, b, c; };             // kind 0: none yet, 1: iso (a = VW), 2: small (NC, spb, tc), 3: dense (a: per-mode)
+static thread_local SampleRecord g_last_sample = {0, 0, 0, 0};
+extern "C" const char* sgpmp_last_sample_kernel(void) {
+    static thread_local char text[64];
+    const SampleRecord& r = g_last_sample;
+    text[0] = 0;
+    if (r.kind == 1) snprintf(text, sizeof(text), "sample_iso_kernel<VW=%d>", r.a);
+    else if (r.kind == 2) snprintf(text, sizeof(text), "sample_iso_small_kernel<NC=%d,spb=%d,tc=%d>", r.a, r.b, r.c);
+    else if (r.kind == 3) snprintf(text, sizeof(text), "sample_dense_kernel%s", r.a ? "(per-mode)" : "");
+    return text;
+}
+
 template <typename real>
 static hipError_t sample_dispatch(int n, int T, const PriorDev& prior, uint64_t seed, uint64_t draw,
                                   const real* means, int n_modes, int mode_offset, int S,
@@ -394,6 +410,7 @@ static hipError_t sample_dispatch(int n, int T, const PriorDev& prior, uint64_t 
                                               mode_offset, seed, draw, out, zero_stats)
             if (n == 2) SMALL_LAUNCH(2); else if (n == 3) SMALL_LAUNCH(3); else if (n == 7) SMALL_LAUNCH(7); else SMALL_LAUNCH(0);
 #undef SMALL_LAUNCH
+            g_last_sample = {2, (n == 2 || n == 3 || n == 7) ? n : 0, spb, tc};
             return hipGetLastError();
         }
         const int wpb = waves < 4 ? waves : 4;
@@ -411,6 +428,7 @@ static hipError_t sample_dispatch(int n, int T, const PriorDev& prior, uint64_t 
         else
             hipLaunchKernelGGL((sample_iso_kernel<real, 4>), grid, block, lds, stream, n, T, S, spw, coef,
                                means, eps, eps_modes, eps_mode_offset, mode_offset, seed, draw, lpr_shift, out, zero_stats);
+        g_last_sample = {1, vw, 0, 0};
         return hipGetLastError();
     }
     const real* G = f64 ? (const real*)prior.G : (const real*)prior.G32;
@@ -421,6 +439,7 @@ static hipError_t sample_dispatch(int n, int T, const PriorDev& prior, uint64_t 
     dim3 grid((S + 63) / 64, n_modes), block(256);       // 4 waves x 16 samples
     hipLaunchKernelGGL((sample_dense_kernel<real>), grid, block, 0, stream, n, T, S, G, H, mode_stride, means, eps,
                        eps_modes, eps_mode_offset, mode_offset, seed, draw, out, zero_stats);
+    g_last_sample = {3, mode_stride != 0, 0, 0};
     return hipGetLastError();
 }
 

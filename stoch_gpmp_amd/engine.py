@@ -416,6 +416,12 @@ class Engine:
                                           eps_mode_offset, L.ptr(out), L.stream_ptr()))
         return out
 
+    def last_sample_kernel(self):
+        """Kernel and launch parameters of this thread's last sampler launch, e.g. "sample_iso_small_kernel<NC=7,spb=8,tc=64>"
+        ("" before the first; include/sgpmp.h: sgpmp_last_sample_kernel).  AttributeError on a library built before the entry
+        point existed (_lib.ADDED_LATER_UNDER_THIS_ABI)."""
+        return self.lib.sgpmp_last_sample_kernel().decode()
+
     def noise(self, seed, draw, n_modes, n_samples, mode_offset=0):
         """The eps the kernels draw for (seed, draw, global particles mode_offset .. + n_modes, samples 0 .. n_samples) in
         torch's randn(n_samples, n_modes, T*d) layout (include/sgpmp.h: sgpmp_noise)."""

@@ -217,7 +217,7 @@ def test_native_noise_statistics_and_sharding_invariance(dtype):
 @pytest.mark.parametrize("n,T,dense", [(2, 9, False), (7, 64, False), (3, 12, True), (2, 70, "standard"),
                                         (7, 33, "standard")])
 def test_native_noise_samples_match_the_restated_stream(monkeypatch, n, T, dense, dtype, rtol):
-    """The in-kernel Philox4x32-10 + Box-Muller stream, restated on the CPU (oracle/native_noise.py,
+    """The in-kernel Philox4x32-7 + Box-Muller stream, restated on the CPU (oracle/native_noise.py,
     pinned by the Random123 known-answer vectors), fed through the oracle's dense sampler must give
     the samples the HIP sampler produces from (seed, draw, global particle index) alone."""
     from oracle.native_noise import native_eps

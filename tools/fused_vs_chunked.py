@@ -1,6 +1,9 @@
 """Fused launch vs sampler + chunked sweep vs sampler + two-trajectory sweep on one trajectory of means: at this small
-size the two-launch paths take sample_iso_small_kernel, whose samples differ from the fused launch's in the last bit
-(one fused multiply-add ordered differently), hence costs differ by ~1.5e-6 relative -- enough to flip a near-tie."""
+size the two-launch paths take sample_iso_small_kernel.  Its samples are sample_iso_kernel's bit for bit (rng.h: scan_step is
+scan_step_noise followed by scan_step_state, every product-sum an explicit fma; tests/test_gpu_sampler.py holds the two kernels to
+torch.equal in both precisions) -- when this tool was written the small kernel still ordered one fused multiply-add differently and
+the "samples a==b" column read False, costs differing by ~1.5e-6 relative, enough to flip a near-tie.  A difference the columns
+below show today comes from the sweeps, not from the sampler."""
 import os, sys
 sys.path.insert(0, os.getcwd())
 import torch
